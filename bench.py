@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Benchmark of the descriptor + matching hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -16,10 +16,15 @@ MX-fp6 (e2m3) images of hi and of lo = v - hi; a product is hi.hi on v_mfma_f32_
 cross terms on ONE v_mfma_scale_f32_32x32x64_f8f6f4 (K-concatenated), fp32 accumulate — 1.5 bf16-MFMA
 times per product instead of the 3 of bf16x3 — and the descriptors stay within north_star's 1e-4 of
 the reference CPU path (tests/test_gpu_mx.py).  Only conv1_1 (K = 27, 0.56 % of the FLOPs; inside the
-fused stem) stays in split bf16 in this mode.  Plain bf16 — descriptors at ~3e-3 — is measured in the same run
-and reported under `fast_mode`, labelled as what it is; `--precision bf16x3` gives round 2's headline.
+fused stem) stays in split bf16 in this mode.  Plain bf16 — descriptors at ~3e-3 — is measured in a `--full`
+run and reported under `fast_mode`, labelled as what it is; `--precision bf16x3` gives round 2's headline.
 
-Rank 0 prints ONE JSON line.  Besides the contract keys it carries
+A plain run sets up, warms up, times the K steps and prints the line: the keys below are null in it, except
+`roofline` when the timed steps run on one lane (`--no-pipeline`, `--eager`).  `--full` measures them too.
+`--dump-outputs DIR` writes the descriptors of the last timed step (rank 0) to DIR/descriptors.npy, float32;
+weights and inputs are seeded, so runs with the same arguments see the same inputs.
+
+Rank 0 prints ONE JSON line.  Besides the contract keys, a `--full` run carries
   roofline      the matrix-core convolution kernels (12 launches per step: the fused stem — conv1_1 +
                 conv1_2 + pool in one launch — and the 11 launches conv2_1..conv5_3, in every matrix-core
                 mode alike): ALGORITHMIC FLOPs of those launches / their measured span, bracketed with
@@ -55,6 +60,7 @@ import threading
 import time
 from pathlib import Path
 
+import numpy as np
 import torch
 
 ROOT = Path(__file__).resolve().parent
@@ -100,9 +106,11 @@ def self_launch_argv(n_gpus, argv, port=None):
             "--master-addr", "127.0.0.1", "--master-port", str(port), str(Path(__file__).resolve()), *argv]
 
 
-def time_extraction(c, model, x, precision, steps, warmup, eager=False, pipeline=True):
+def time_extraction(c, model, x, precision, steps, warmup, eager=False, pipeline=True, span_leg=True):
     """K timed steps of the descriptor path in `precision`: barrier + synchronize on both sides, max
-    over ranks.  Returns the result dict (value = images/s over all ranks)."""
+    over ranks.  Returns the result dict (value = images/s over all ranks; "out" = a copy of the
+    descriptors of the last timed step).  span_leg=False leaves out the one-lane region of the
+    roofline: with two lanes the result then carries no roofline."""
     dev, dist = c.dev, c.dist
     model.set_precision(precision)
     ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(steps)]
@@ -133,7 +141,7 @@ def time_extraction(c, model, x, precision, steps, warmup, eager=False, pipeline
                 assert all(torch.equal(g_, ref) for g_ in got), "graph replay differs from the eager forward"
                 launch_mode = ("hipGraph x2 per step, step i on lane i % 2 (two streams in flight)"
                                if pipeline else "hipGraph x2 per step")
-                if pipeline:
+                if pipeline and span_leg:
                     fwd1 = model.graphed(x, pipeline=False)
                     assert torch.equal(fwd1(), ref), "one-lane graph replay differs from the eager forward"
             except Exception as e:      # capture unsupported on this stack: time the eager launches
@@ -150,17 +158,20 @@ def time_extraction(c, model, x, precision, steps, warmup, eager=False, pipeline
         # W untimed warm-up steps of exactly the timed path, issued right before the timed region:
         # after ~20 ms of idling (graph instantiation, the host-side checks above) the chip needs
         # ~15 ms of work to return to its sustained clocks (tests/gpu_graph_overhead.py)
+        # the span comes from the timed steps themselves unless their launches overlap on two lanes
+        span_in_region = fwd is None or not pipeline
         c.barrier()                     # the first RCCL barrier builds its channels: not before t0
         for _ in range(max(warmup, 0)):
             step(None)
         c.barrier()
         t0 = time.perf_counter()
         for k in range(steps):
-            out = step(None if fwd1 is not None else ev[k])
+            out = step(ev[k] if span_in_region else None)
         if fwd is not None:
             fwd.wait()                  # f16mx: the range flags of the last two batches are checked INSIDE the region
         c.barrier()
         t1 = time.perf_counter()
+        last = out.clone()              # what the caller of the last timed step received
         model.base_model.profile_events = None
         elapsed = torch.tensor([t1 - t0], dtype=torch.float64, device=dev)
         if c.use_dist:
@@ -185,6 +196,15 @@ def time_extraction(c, model, x, precision, steps, warmup, eager=False, pipeline
             assert torch.equal(out, ref), "one-lane timed forward differs from model(x)"
     batch = int(x.shape[0])
     value = batch * steps * c.world / elapsed
+    runs = {k_: v_ - runs0.get(k_, 0) for k_, v_ in bm.precision_runs.items() if v_ - runs0.get(k_, 0)}
+    res = {"value": round(value, 2), "ms_per_step": round(elapsed / steps * 1e3, 4),
+           "launch": launch_mode, "roofline": None, "dtype": precision,
+           "range_fallbacks": int(timed_fallbacks + (fwd1.range_fallbacks if fwd1 is not None else 0)),
+           "range_fallbacks_timed_region": int(timed_fallbacks), "timed_batches": int(steps),
+           # backbone passes by the arithmetic they RAN in, eager + captured (a replay repeats its capture's)
+           "precision_runs": runs, "out": last}
+    if not span_in_region and fwd1 is None:
+        return res                      # two lanes and no span leg: no span to put a roofline on
     span_ms = sum(a.elapsed_time(b) for a, b in ev) / len(ev)
     # launches inside the span and their algorithmic FLOPs (2 flop per MAC of the convolution; the
     # hi/lo split of bf16x3 is an implementation detail of the arithmetic, not more algorithm)
@@ -268,13 +288,8 @@ def time_extraction(c, model, x, precision, steps, warmup, eager=False, pipeline
         c11 = conv11_flops_per_image() / (igemm_flops_per_image() + conv11_flops_per_image())
         roof["matrix_pipe_time_per_product_vs_bf16"] = round((1.0 - c11) * 1.5 + c11 * 3.0 * 32.0 / 27.0, 3)
         roof["issued_frac"] = round(roof["matrix_pipe_time_per_product_vs_bf16"] * achieved / peak, 4)
-    runs = {k_: v_ - runs0.get(k_, 0) for k_, v_ in bm.precision_runs.items() if v_ - runs0.get(k_, 0)}
-    return {"value": round(value, 2), "ms_per_step": round(elapsed / steps * 1e3, 4),
-            "launch": launch_mode, "roofline": roof, "dtype": precision,
-            "range_fallbacks": int(timed_fallbacks + (fwd1.range_fallbacks if fwd1 is not None else 0)),
-            "range_fallbacks_timed_region": int(timed_fallbacks), "timed_batches": int(steps),
-            # backbone passes by the arithmetic they RAN in, eager + captured (a replay repeats its capture's)
-            "precision_runs": runs}
+    res["roofline"] = roof
+    return res
 
 
 class _MemLoader:
@@ -537,8 +552,13 @@ def sustain(c, model, x, precision, seconds):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=30)
+    ap.add_argument("--steps", type=int, default=30, help="number of timed steps (>= 1)")
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the roofline's one-lane span leg, "
+                         "fast_mode, api, matching and cpu_baseline (a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the descriptors of the last timed step to DIR/descriptors.npy (float32)")
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--precision", default="f16mx", choices=["bf16", "f16mx", "bf16x3", "fp32"],
                     help="arithmetic of the headline line (default: f16mx, the fastest mode inside 1e-4)")
@@ -554,6 +574,8 @@ def main():
     ap.add_argument("--gallery", type=int, default=81920)
     ap.add_argument("--sustain", type=float, default=0.0, help="sustained-run mode: replay for >= S seconds")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "RANK" not in os.environ:
         # `python bench.py --gpus N` launches its N ranks itself — one process per GPU under
@@ -620,17 +642,26 @@ def main():
         return
 
     head = time_extraction(c, model, x, args.precision, args.steps, args.warmup, eager=args.eager,
-                           pipeline=not args.no_pipeline)
+                           pipeline=not args.no_pipeline, span_leg=args.full)
+    out = head.pop("out")
+    if args.dump_outputs and c.rank == 0:
+        # rank 0's (32, 4096) descriptors, 512 KiB: the inputs and weights are seeded, so two builds compare output
+        # for output
+        d = Path(args.dump_outputs)
+        d.mkdir(parents=True, exist_ok=True)
+        np.save(d / "descriptors.npy", out.float().cpu().numpy())
+
     fast = None
-    if not args.skip_fast_mode and args.precision != "bf16":
+    if args.full and not args.skip_fast_mode and args.precision != "bf16":
         fast = time_extraction(c, model, x, "bf16", args.steps, args.warmup, eager=args.eager,
                                pipeline=not args.no_pipeline)
+        fast.pop("out")
         fast["note"] = ("plain bf16 operands: descriptors at ~3e-3 relative of the reference (NOT the 1e-4 "
                         "mode), a third of the matrix work")
         fast["unit"] = "images/s"
 
     api = None
-    if not args.skip_api and c.rank == 0:
+    if args.full and not args.skip_api and c.rank == 0:
         api = {}
         with torch.no_grad():
             api[args.precision] = time_api(c, model, args.precision, args.batch, args.api_batches, u8=False)
@@ -642,13 +673,13 @@ def main():
     barrier()
 
     matching = None
-    if not args.skip_matching:
+    if args.full and not args.skip_matching:
         matching = time_matching(c, args.precision, args.queries, args.gallery)
         if args.precision != "bf16":
             matching["fast_mode"] = time_matching(c, "bf16", args.queries, args.gallery)
 
     cpu = None
-    if c.rank == 0 and c.world == 1 and not args.skip_cpu_baseline:
+    if args.full and c.rank == 0 and c.world == 1 and not args.skip_cpu_baseline:
         cpu, cpu_match = cpu_baselines()
         if matching is not None:
             matching["cpu_baseline"] = cpu_match
@@ -658,7 +689,7 @@ def main():
             "metric": "descriptors_per_sec", "value": head["value"], "unit": "images/s",
             "n_gpus": c.world, "rccl_ranks_seen": ranks_seen, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": head["ms_per_step"], "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": args.precision, "data": "synthetic",
+            "scaling": "weak", "vs_baseline": None, "dtype": args.precision, "data": "synthetic", "full": args.full,
             "config": {"workload": "batch=32 VGG16-conv5 + NetVLAD(64x512) + PCA-4096 descriptor "
                                    "extraction, 32 distinct synthetic 480x640 inputs per rank resident in "
                                    "HBM (BASELINE.json configs[1])",

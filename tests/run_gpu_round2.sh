@@ -18,15 +18,15 @@ if [ -z "$QUICK" ]; then
   tail -n 5 $OUT/pytest_gpu.log
   timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1; echo "smoke exit $?" | tee -a $OUT/smoke.log
 fi
-timeout 900 python bench.py 2> $OUT/bench_err.log | tee $OUT/bench.json | cut -c1-400
+timeout 900 python bench.py --full 2> $OUT/bench_err.log | tee $OUT/bench.json | cut -c1-400
 # the launch line the driver uses for N > 1, with one rank: RCCL init / barrier / all-reduce path
 timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29541 \
-  bench.py --gpus 1 --steps 10 --warmup 3 --skip-cpu-baseline --skip-api 2> $OUT/bench_torchrun_err.log | tee $OUT/bench_torchrun.json | cut -c1-300
+  bench.py --full --gpus 1 --steps 10 --warmup 3 --skip-cpu-baseline --skip-api 2> $OUT/bench_torchrun_err.log | tee $OUT/bench_torchrun.json | cut -c1-300
 # flow check of the N = 2 launch line on this one-GPU box: two ranks share the GPU over gloo (the
 # numbers mean nothing; what is checked is that the line comes out: barrier / max-reduce / sharded
 # matching with two real ranks)
 OIBL_BENCH_SHARED_GPU=1 timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29543 \
-  bench.py --gpus 2 --steps 5 --warmup 2 --skip-cpu-baseline --skip-api 2> $OUT/bench_2ranks_shared_err.log | tee $OUT/bench_2ranks_shared.json | cut -c1-300
+  bench.py --full --gpus 2 --steps 5 --warmup 2 --skip-cpu-baseline --skip-api 2> $OUT/bench_2ranks_shared_err.log | tee $OUT/bench_2ranks_shared.json | cut -c1-300
 for p in bf16x3 bf16; do
   timeout 600 python tests/gpu_timing.py --batch 32 --precision $p 2>&1 | grep -v amdgpu.ids | tee $OUT/timing_$p.log
 done
@@ -56,7 +56,7 @@ for p in bf16x3 bf16; do
   fi
 done
 if [ -z "$QUICK" ]; then
-  timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_match -o bench -- python $R/bench.py --steps 2 --warmup 1 --skip-cpu-baseline --skip-api > $OUT/prof_match.log 2>&1
+  timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_match -o bench -- python $R/bench.py --full --steps 2 --warmup 1 --skip-cpu-baseline --skip-api > $OUT/prof_match.log 2>&1
 fi
 cd $R
 if [ -z "$QUICK" ]; then

@@ -18,13 +18,13 @@ if [ -z "$QUICK" ]; then
   tail -n 5 $OUT/pytest_gpu.log
   timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1; echo "smoke exit $?" | tee -a $OUT/smoke.log
 fi
-timeout 900 python bench.py 2> $OUT/bench_err.log | tee $OUT/bench.json | cut -c1-400
+timeout 900 python bench.py --full 2> $OUT/bench_err.log | tee $OUT/bench.json | cut -c1-400
 # the launch line the driver uses for N > 1, with one rank: RCCL init / barrier / all-reduce path
 timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29541 \
-  bench.py --gpus 1 --steps 10 --warmup 3 --skip-cpu-baseline --skip-api 2> $OUT/bench_torchrun_err.log | tee $OUT/bench_torchrun.json | cut -c1-300
+  bench.py --full --gpus 1 --steps 10 --warmup 3 --skip-cpu-baseline --skip-api 2> $OUT/bench_torchrun_err.log | tee $OUT/bench_torchrun.json | cut -c1-300
 # `python bench.py --gpus 2` launches its two ranks itself; on this one-GPU box they share the GPU over gloo
 # (flow check of barrier / max-reduce / sharded matching with two real ranks; the numbers mean nothing)
-OIBL_BENCH_SHARED_GPU=1 timeout 600 python bench.py --gpus 2 --steps 5 --warmup 2 --skip-cpu-baseline --skip-api \
+OIBL_BENCH_SHARED_GPU=1 timeout 600 python bench.py --full --gpus 2 --steps 5 --warmup 2 --skip-cpu-baseline --skip-api \
   2> $OUT/bench_2ranks_shared_err.log | tee $OUT/bench_2ranks_shared.json | cut -c1-300
 timeout 600 python tests/gpu_precbench.py 2>&1 | grep -v amdgpu.ids | tee $OUT/precbench.log
 if [ -z "$QUICK" ]; then
@@ -49,7 +49,7 @@ done
 if [ -z "$QUICK" ]; then
   timeout 600 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/prof_fetch_f16mx -o bench -- python $R/bench.py --precision f16mx --steps 5 --warmup 2 $SKIP > $OUT/prof_fetch_f16mx.log 2>&1
   timeout 600 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $OUT/prof_write_f16mx -o bench -- python $R/bench.py --precision f16mx --steps 5 --warmup 2 $SKIP > $OUT/prof_write_f16mx.log 2>&1
-  timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_match -o bench -- python $R/bench.py --steps 2 --warmup 1 --skip-cpu-baseline --skip-api > $OUT/prof_match.log 2>&1
+  timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_match -o bench -- python $R/bench.py --full --steps 2 --warmup 1 --skip-cpu-baseline --skip-api > $OUT/prof_match.log 2>&1
 fi
 cd $R
 # keep the merged output small: drop per-dispatch traces larger than 8 MiB

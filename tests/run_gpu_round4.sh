@@ -19,10 +19,10 @@ if [ -z "$QUICK" ]; then
   tail -n 5 $OUT/pytest_gpu.log
   timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1; echo "smoke exit $?" | tee -a $OUT/smoke.log
 fi
-timeout 900 python bench.py 2> $OUT/bench_err.log | tee $OUT/bench.json | cut -c1-400
+timeout 900 python bench.py --full 2> $OUT/bench_err.log | tee $OUT/bench.json | cut -c1-400
 timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29541 \
-  bench.py --gpus 1 --steps 10 --warmup 3 --skip-cpu-baseline --skip-api 2> $OUT/bench_torchrun_err.log | tee $OUT/bench_torchrun.json | cut -c1-300
-OIBL_BENCH_SHARED_GPU=1 timeout 600 python bench.py --gpus 2 --steps 5 --warmup 2 --skip-cpu-baseline --skip-api \
+  bench.py --full --gpus 1 --steps 10 --warmup 3 --skip-cpu-baseline --skip-api 2> $OUT/bench_torchrun_err.log | tee $OUT/bench_torchrun.json | cut -c1-300
+OIBL_BENCH_SHARED_GPU=1 timeout 600 python bench.py --full --gpus 2 --steps 5 --warmup 2 --skip-cpu-baseline --skip-api \
   2> $OUT/bench_2ranks_shared_err.log | tee $OUT/bench_2ranks_shared.json | cut -c1-300
 timeout 600 python tests/gpu_precbench.py 2>&1 | grep -v amdgpu.ids | tee $OUT/precbench.log
 if [ -z "$QUICK" ]; then
@@ -48,14 +48,14 @@ if [ -z "$QUICK" ]; then
     timeout 600 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/prof_fetch_$p -o bench -- python $R/bench.py --precision $p --steps 5 --warmup 2 $SKIP > $OUT/prof_fetch_$p.log 2>&1
     timeout 600 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $OUT/prof_write_$p -o bench -- python $R/bench.py --precision $p --steps 5 --warmup 2 $SKIP > $OUT/prof_write_$p.log 2>&1
   done
-  timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_match -o bench -- python $R/bench.py --steps 2 --warmup 1 --skip-cpu-baseline --skip-api > $OUT/prof_match.log 2>&1
+  timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_match -o bench -- python $R/bench.py --full --steps 2 --warmup 1 --skip-cpu-baseline --skip-api > $OUT/prof_match.log 2>&1
   # where a single image's time goes (200 eager forwards each)
   for cfg in "f16mx 480 640" "f16mx 224 224" "bf16x3 224 224"; do
     set -- $cfg
     timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_single_$1_$2 -o one -- python $R/tests/gpu_small_sizes.py --loop $1 $2 $3 1 > $OUT/prof_single_$1_$2.log 2>&1
   done
   # MFMA busy / clock / L2 hit / LDS bank conflicts per kernel (tools/pmc_summary.py): counters only, separate passes
-  CMD="python $R/bench.py --precision f16mx --steps 3 --warmup 1 --eager --skip-cpu-baseline --skip-api --skip-fast-mode"
+  CMD="python $R/bench.py --full --precision f16mx --steps 3 --warmup 1 --eager --skip-cpu-baseline --skip-api --skip-fast-mode"
   i=0
   for set in "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE" \
              "GRBM_GUI_ACTIVE TCC_HIT_sum TCC_MISS_sum"; do
