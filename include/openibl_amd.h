@@ -286,6 +286,27 @@ int oibl_netvlad_forward(const void* feat, int N, int P, int K, int C, int preci
                          float* vlad_raw, float* vlad_norm, void* ws, size_t ws_bytes,
                          void* stream);
 
+/* ---- SFRS region similarities (forward only) ---------------------------------------- *
+ * Replaces EmbedRegionNet._compute_region_sim (ibl/models/netvlad.py:123-186), which SFRSTrainer._forward
+ * calls on the frozen previous-generation model under torch.no_grad() (ibl/trainers.py:243-244).
+ * The conv5_3 map of an image is cut into four quarters of h/2 x w/2 pixels (q0 top-left, q1 top-right, q2
+ * bottom-left, q3 bottom-right); NetVLAD (as above, same per-pixel normalisation and softmax) is aggregated over
+ * each quarter's pixels; 9 regions are sums of quarters, in this order:
+ *   [q0+q1+q2+q3, q0+q1, q2+q3, q0+q2, q1+q3, q0, q1, q2, q3]
+ * each intra-normalised per cluster, flattened k-major and L2-normalised (eps 1e-12).
+ * oibl_region_vlad_forward: feat [N][h][w][C] fp32 (precision must be OIBL_F32; h and w even, K = 64, C = 512)
+ *   -> region_vlad [N][9][K*C] fp32.  The map is read once; an image's vectors do not depend on the batch it is
+ *   computed in (bit for bit).  Workspace from oibl_region_workspace_bytes (0 for an invalid shape).
+ * oibl_region_scores: region_vlad [T*per_tuple][9][L], tuple-major, the first image of each tuple is the anchor,
+ *   per_tuple = 1 + n >= 2 -> score [T][n][9][9] fp32,
+ *   score[t][j][a][b] = <region_vlad[t*per_tuple][a], region_vlad[t*per_tuple + 1 + j][b]>, summed in a fixed order.
+ * Invalid arguments (odd h or w, per_tuple < 2, short workspace) return an error status and launch nothing.   */
+size_t oibl_region_workspace_bytes(int N, int h, int w, int K, int C);
+int oibl_region_vlad_forward(const void* feat, int N, int h, int w, int K, int C, int precision,
+                             const float* assign_w, const float* centroids, int normalize_input,
+                             float* region_vlad, void* ws, size_t ws_bytes, void* stream);
+int oibl_region_scores(const float* region_vlad, int T, int per_tuple, int L, float* score, void* stream);
+
 /* ---- PCA-whitening projection + L2 ------------------------------------------------ *
  * Replaces EmbedNetPCA.pca_layer + F.normalize (netvlad.py:105-108) and PCA.infer
  * (ibl/pca.py:108-123):  y = normalize(W v + b).

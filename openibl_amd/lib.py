@@ -57,6 +57,10 @@ SIGNATURES = {
     "oibl_netvlad_forward": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p,
                                      c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_size_t,
                                      c_void_p]),
+    "oibl_region_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "oibl_region_vlad_forward": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
+                                         c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "oibl_region_scores": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "oibl_pca_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "oibl_pca_forward": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int,
                                  c_void_p, c_void_p, c_size_t, c_void_p]),

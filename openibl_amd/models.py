@@ -422,8 +422,11 @@ def GraphedDescriptor(model: "EmbedNetPCA", example: torch.Tensor, pipeline: boo
 
 
 class EmbedRegionNet(_PrecisionMixin, nn.Module):
-    """ibl/models/netvlad.py:112-207.  Only the evaluation branch (:199-205, identical to
-    EmbedNet.forward) is implemented; the SFRS region-similarity training branch is out of scope."""
+    """ibl/models/netvlad.py:112-207.  forward() is the evaluation branch (:199-205, identical to
+    EmbedNet.forward).  The SFRS region-similarity branch (:123-194) is forward-only here — the reference runs it
+    on the frozen previous-generation model under torch.no_grad() (ibl/trainers.py:243-244) — and is reached
+    through `region_similarity(x)`; forward() in training mode keeps raising: this package has no autograd, and
+    gradient-free tensors handed to a trainer would be a trap."""
 
     def __init__(self, base_model, net_vlad, tuple_size=1):
         super().__init__()
@@ -439,12 +442,70 @@ class EmbedRegionNet(_PrecisionMixin, nn.Module):
     def forward(self, x):
         if self.training:
             raise NotImplementedError("EmbedRegionNet: the SFRS training branch is not part of the "
-                                      "MI355X inference path; call .eval() first")
+                                      "MI355X inference path; call .eval() first (the forward-only region "
+                                      "similarities of a frozen model: region_similarity(x))")
         return _with_range_guard(self.base_model, x, self._head)
 
     def _head(self, feat):
         _, vlad = self.net_vlad.aggregate_nhwc(feat, want_raw=False, want_norm=True)
         return ops.global_maxpool_nhwc(feat), vlad
+
+    def _tuple_shape(self, batch: int):
+        T = int(self.tuple_size)
+        if T <= 0 or batch % T:
+            raise ValueError(f"EmbedRegionNet: a batch of {batch} images is not a multiple of tuple_size {T}")
+        if batch // T < 2:
+            raise ValueError(f"EmbedRegionNet: a tuple needs an anchor and at least one pair "
+                             f"(batch {batch}, tuple_size {T}: {batch // T} image per tuple)")
+        return T, batch // T
+
+    def _region_head(self, feat):
+        """conv5_3 map [T*(1+n)][h][w][C] (NHWC), tuple-major, anchor first -> (score, vlad_A, vlad_B)."""
+        T, per = self._tuple_shape(int(feat.shape[0]))
+        w, c = self.net_vlad._params()
+        vec = ops.region_vlad(feat, w, c, self.net_vlad.normalize_input)
+        score = ops.region_scores(vec, T)
+        vec = vec.view(T, per, 9, vec.shape[-1])
+        return score, vec[:, :1], vec[:, 1:]
+
+    @torch.no_grad()
+    def region_similarity(self, x):
+        """The reference's training-mode forward (_forward_train, netvlad.py:188-194), without gradients, in
+        either module mode.  x: images [T*(1+n)][3][H][W], tuple-major, the first image of each tuple is the
+        anchor (T = tuple_size, n >= 1 pairs per tuple); H // 16 and W // 16 must be even.  Returns
+          score  [T][n][9][9]  score[t, j, a, b] = <vlad_A[t, 0, a], vlad_B[t, j, b]>,
+          vlad_A [T][1][9][L], vlad_B [T][n][9][L]   (L = num_clusters * dim; views of one [T][1+n][9][L] tensor),
+        fp32 on the device; the 9 regions are [whole, top, bottom, left, right, q0 (top-left), q1 (top-right),
+        q2 (bottom-left), q3 (bottom-right)].  The reference's own arithmetic only runs with tuple_size == 1; here
+        tuple_size > 1 is the tuple_size == 1 result per tuple, stacked."""
+        if x.dim() != 4:
+            raise ValueError("EmbedRegionNet.region_similarity: images [N][3][H][W]")
+        self._tuple_shape(int(x.shape[0]))
+        H, W = (int(x.shape[1]), int(x.shape[2])) if x.dtype == torch.uint8 else (int(x.shape[2]), int(x.shape[3]))
+        h, w = ops.vgg16_feature_hw(H, W)
+        if h % 2 or w % 2:
+            raise ValueError(f"EmbedRegionNet.region_similarity: the conv5 map of a {H} x {W} image is {h} x {w}, "
+                             f"both sides must be even to cut it into quarters")
+        return _with_range_guard(self.base_model, x, self._region_head)
+
+    @torch.no_grad()
+    def _compute_region_sim(self, feature_A, feature_B):
+        """The reference's entry for callers that hold conv5 maps (netvlad.py:123): feature_A [T][C][h][w] the
+        anchors' maps, feature_B [T*n][C][h][w] the pairs' maps (NCHW fp32) -> (score, vlad_A, vlad_B) as
+        region_similarity returns them."""
+        T = int(self.tuple_size)
+        if feature_A.dim() != 4 or feature_B.dim() != 4 or int(feature_A.shape[0]) != T:
+            raise ValueError(f"EmbedRegionNet._compute_region_sim: feature_A must hold tuple_size = {T} maps [C][h][w]")
+        if int(feature_B.shape[0]) == 0 or int(feature_B.shape[0]) % T:
+            raise ValueError(f"EmbedRegionNet._compute_region_sim: {int(feature_B.shape[0])} pair maps are not a "
+                             f"positive multiple of tuple_size {T}")
+        n = int(feature_B.shape[0]) // T
+        maps = torch.cat([feature_A.float().unsqueeze(1), feature_B.float().view(T, n, *feature_B.shape[1:])], dim=1)
+        h, w = int(maps.shape[-2]), int(maps.shape[-1])
+        if h % 2 or w % 2:
+            raise ValueError(f"EmbedRegionNet._compute_region_sim: the map is {h} x {w}, both sides must be even")
+        feat = ops.nchw_f32_to_nhwc(maps.flatten(0, 1).contiguous(), "fp32")
+        return self._region_head(feat)
 
 
 _factory = {

@@ -489,6 +489,53 @@ def netvlad(feat: torch.Tensor, assign_w: torch.Tensor, centroids: torch.Tensor,
     return raw, nrm
 
 
+# ---- SFRS region similarities ---------------------------------------------------------------------
+def region_vlad(feat: torch.Tensor, assign_w: torch.Tensor, centroids: torch.Tensor,
+                normalize_input: bool = True) -> torch.Tensor:
+    """feat [N][h][w][C] fp32 or bf16 (widened to fp32: the region head is fp32), h and w even -> [N][9][K*C] fp32:
+    the intra- and L2-normalised NetVLAD of the whole image, its four halves and its four quarters
+    (EmbedRegionNet._compute_region_sim, ibl/models/netvlad.py:123-175).  An image's vectors do not depend on the
+    batch it is computed in."""
+    dev = _need_cuda(feat, assign_w, centroids)
+    if feat.dim() != 4 or feat.dtype not in (torch.bfloat16, torch.float32):
+        raise ValueError("region_vlad: feature map must be a bf16 or fp32 [N][h][w][C] tensor")
+    N, h, w, C_ = map(int, feat.shape)
+    if h % 2 or w % 2 or h == 0 or w == 0:
+        raise ValueError(f"region_vlad: the conv5 map is {h} x {w}, both sides must be even to cut it into quarters")
+    feat = feat.float().contiguous()
+    K = int(centroids.shape[0])
+    aw = assign_w.reshape(K, C_)
+    if aw.dtype != torch.float32 or centroids.dtype != torch.float32 or not aw.is_contiguous() \
+            or not centroids.is_contiguous():
+        raise ValueError("region_vlad: assign_w / centroids must be contiguous float32")
+    lib = _lib.load()
+    ws = workspace(lib.oibl_region_workspace_bytes(N, h, w, K, C_), dev, "region")
+    out = torch.empty((N, 9, K * C_), dtype=torch.float32, device=dev)
+    _lib.check(lib.oibl_region_vlad_forward(_ptr(feat), N, h, w, K, C_, F32, _ptr(aw), _ptr(centroids),
+                                            int(normalize_input), _ptr(out), _ptr(ws), ws.numel(), _stream(dev)),
+               "region_vlad_forward")
+    return out
+
+
+def region_scores(region_vlad: torch.Tensor, tuple_size: int) -> torch.Tensor:
+    """region_vlad [T*(1+n)][9][L] fp32, tuple-major with the anchor first -> score [T][n][9][9],
+    score[t, j, a, b] = <region a of tuple t's anchor, region b of its pair j> (netvlad.py:177-184)."""
+    dev = _need_cuda(region_vlad)
+    if region_vlad.dim() != 3 or int(region_vlad.shape[1]) != 9 or region_vlad.dtype != torch.float32 \
+            or not region_vlad.is_contiguous():
+        raise ValueError("region_scores: a contiguous float32 [N][9][L] tensor")
+    N, _, L = map(int, region_vlad.shape)
+    T = int(tuple_size)
+    if T <= 0 or N % T:
+        raise ValueError(f"region_scores: {N} images are not a multiple of tuple_size {T}")
+    if N // T < 2:
+        raise ValueError(f"region_scores: a tuple needs an anchor and at least one pair (got {N // T} image per tuple)")
+    score = torch.empty((T, N // T - 1, 9, 9), dtype=torch.float32, device=dev)
+    _lib.check(_lib.load().oibl_region_scores(_ptr(region_vlad), T, N // T, L, _ptr(score), _stream(dev)),
+               "region_scores")
+    return score
+
+
 # ---- PCA --------------------------------------------------------------------------------------
 class PcaWeight:
     """A PCA weight [d][D] resident on the device, with — fp32 only — the re-packed copy the streaming kernel
