@@ -507,6 +507,50 @@ int oibl_first_hit_rank(const int32_t* topk_idx, int m, int k, const int32_t* gt
                         const int32_t* gt_values, const int32_t* gallery_pids, int nms_window,
                         int32_t* out_rank, void* stream);
 
+/* ---- k-reciprocal re-ranking from descriptor rows -------------------------------------- *
+ * Replaces re_ranking (ibl/utils/rerank.py:32-100; Evaluator.evaluate(rerank=True), ibl/evaluators.py:190-200, and
+ * the SFRS trainer's update_sampler(rerank=True)) without its dense (Q+G) x (Q+G) arrays.  X = [queries; gallery],
+ * n = Q + G rows of d floats; D[i][j] = (|x_i|^2 + |x_j|^2) - 2 x_i.x_j; O[i][j] = D[i][j]^2 / m_i.  One entry per
+ * stage, in the order a caller runs them (openibl_amd/rerank.py: re_ranking_features); the neighbour lists `rank`
+ * [n][ld] int32 (nearest first, the item itself included, -1 = none) come from oibl_sqdist_topk* of X against X.
+ * Limits: k1 <= 31, k2 <= 8, (k1 + 1)(half + 2) <= 576.  No floating-point atomics: results are bit-identical from
+ * run to run.
+ *   oibl_rerank_row_extremes  x [n][d] fp32 (d % 32 == 0) -> norms [n] = |x_i|^2 and rowmax [n] = m_i =
+ *       max(dmax_i^2, dmin_i^2) over row i of D, contracted in fp32 on the matrix cores; D is never written.
+ *   oibl_rerank_set_stride    (k1 + 1)(half + 2): the most members a set can have; 0 beyond the limits.
+ *   oibl_rerank_sets          half = round(k1 / 2).  idx [n][stride] <- per item the k1-reciprocal set (j among the
+ *       k1 + 1 nearest of i with i among the k1 + 1 nearest of j), expanded by the half-reciprocal set of each member
+ *       when 3 |sub & base| > 2 |sub| (rerank.py:58-65), sorted ascending without repeats; cnt [n] <- its size.
+ *   oibl_rerank_weights       val [n][stride] <- exp(-O[i][idx[i][t]]) / sum over the set (rerank.py:68-69), every
+ *       distance recomputed from the two rows with a fp32 dot product.
+ *   oibl_rerank_expand        k2 > 1 (rerank.py:71-75): (idx2, val2, cnt2) [n][stride2 >= k2 * stride] <- the mean of
+ *       the sparse rows of the k2 nearest items of i, summed in rank order.
+ *   oibl_rerank_invert        nnz = sum of cnt (the caller adds it up).  col_off [n + 1], inv_row / inv_val [nnz] <-
+ *       per column c the rows i that hold it, ascending, and their values (rerank.py:78-80).
+ *   oibl_rerank_jaccard       dist [Q][ldd]: on entry D of the query rows against the GALLERY rows (X[Q..n)), on
+ *       return (1 - lambda) (1 - s / (2 - s)) + lambda D^2 / m_i with s[i][j] = sum_c min(V[i][c], V[Q + j][c]),
+ *       added in ascending c (rerank.py:82-98); each product, quotient and sum rounded to fp32 on its own, as numpy
+ *       does.  one_minus_lambda is passed beside lambda so that both are the caller's fp32 roundings.      */
+size_t oibl_rerank_row_extremes_workspace_bytes(int n, int d);
+int oibl_rerank_row_extremes(const float* x, int n, int d, float* norms, float* rowmax, void* ws, size_t ws_bytes,
+                             void* stream);
+int oibl_rerank_set_stride(int k1, int half);
+int oibl_rerank_sets(const int32_t* rank, int ld, int n, int k1, int half, int32_t* idx, int32_t* cnt, int stride,
+                     void* stream);
+int oibl_rerank_weights(const float* x, const float* norms, const float* rowmax, int n, int d, const int32_t* idx,
+                        const int32_t* cnt, int stride, float* val, void* stream);
+int oibl_rerank_expand(const int32_t* rank, int ld, int n, int k2, const int32_t* idx, const float* val,
+                       const int32_t* cnt, int stride, int32_t* idx2, float* val2, int32_t* cnt2, int stride2,
+                       void* stream);
+size_t oibl_rerank_invert_workspace_bytes(int n, size_t nnz);
+int oibl_rerank_invert(const int32_t* idx, const float* val, const int32_t* cnt, int stride, int n, size_t nnz,
+                       int32_t* col_off, int32_t* inv_row, float* inv_val, void* ws, size_t ws_bytes, void* stream);
+size_t oibl_rerank_jaccard_workspace_bytes(int Q, int G);
+int oibl_rerank_jaccard(const int32_t* idx, const float* val, const int32_t* cnt, int stride, const int32_t* col_off,
+                        const int32_t* inv_row, const float* inv_val, const float* rowmax, int Q, int G,
+                        float one_minus_lambda, float lambda, float* dist, size_t ldd, void* ws, size_t ws_bytes,
+                        void* stream);
+
 /* ---- k-means centroid initialisation (f4) -------------------------------------------- *
  * examples/cluster.py:110-115 runs scikit-learn's KMeans(num_clusters, max_iter = 100,
  * random_state = seed) on 50 000 L2-normalised conv5 descriptors.  The assignment step of a Lloyd

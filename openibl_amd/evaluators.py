@@ -299,10 +299,15 @@ def evaluate_all(distmat, gt, gallery, recall_topk=[1, 5, 10], nms=False):
 
 
 class Evaluator(object):
-    def __init__(self, model, precision: Optional[str] = None, scales=None, descriptor_dtype=None):
+    def __init__(self, model, precision: Optional[str] = None, scales=None, descriptor_dtype=None,
+                 device_rerank: bool = False):
         """`scales` / `descriptor_dtype` are the BASELINE.json configs[4] extensions (multi-scale
-        extraction, 16-bit descriptor storage); the defaults reproduce the reference."""
+        extraction, 16-bit descriptor storage); the defaults reproduce the reference.
+        `device_rerank=True` makes evaluate(rerank=True) re-rank on the device from the resident
+        descriptors (rerank.re_ranking_features: no dense (Q+G) x (Q+G) array, any gallery size the
+        top-k path serves) instead of the reference's host flow; single rank only."""
         super(Evaluator, self).__init__()
+        self.device_rerank = bool(device_rerank)
         self.model = model
         self.rank = _rank_world()[0]
         self.precision = precision
@@ -375,9 +380,61 @@ class Evaluator(object):
             _print_recalls(recalls, recall_topk)
         return recalls
 
+    # -- re-ranking on the device: descriptors stay resident, no (Q+G) x (Q+G) array ----------------
+    def _evaluate_device_rerank(self, query_loader, dataset, query, gallery, ground_truth, gallery_loader,
+                                vlad, pca, gpu, nms, rr_topk, lambda_value, recall_topk=(1, 5, 10)):
+        from .rerank import re_ranking_features
+        rank, world = _rank_world()
+        if world != 1:
+            raise RuntimeError(
+                f"Evaluator(device_rerank=True): re-ranking on the device runs on a single rank (world size "
+                f"{world}): the union of queries and gallery is not sharded yet; use device_rerank=False for "
+                "the reference's host flow")
+        ops.rerank_check_limits(rr_topk, 1)
+        if not torch.cuda.is_available():
+            raise ops._lib.OpenIBLAmdError("openibl_amd: Evaluator(device_rerank=True) runs only on an AMD GPU "
+                                           "through the HIP extension (there is no CPU fallback)")
+        ext = (vlad, pca, gpu, 10, rank, self.scales, self.descriptor_dtype)
+        if gallery_loader is not None:
+            q_feat = _extract_local(self.model, query_loader, *ext)[:len(query)]
+            g_feat = _extract_local(self.model, gallery_loader, *ext)[:len(gallery)]
+        else:
+            # one loader over `dataset`: rows in dataset order, looked up by file name like the host flow
+            feats = _extract_local(self.model, query_loader, *ext)[:len(dataset)]
+            where = {f: i for i, (f, *_) in enumerate(dataset)}
+            dev = feats.device
+            q_feat = feats[torch.as_tensor([where[f] for f, *_ in query], device=dev)]
+            g_feat = feats[torch.as_tensor([where[f] for f, *_ in gallery], device=dev)]
+        k = min(max(recall_topk) * (12 if nms else 1), len(gallery))
+        _check_prefix(k)
+        prec = self.precision or default_precision()
+        pids = [g[1] for g in gallery]
+        if rank == 0:
+            print("===> Start calculating pairwise distances")
+        route = ops.topk_precision(prec, q_feat.dtype, k)
+        _, idx = ops.sqdist_topk(q_feat.contiguous(), g_feat.contiguous(), k, precision=route)
+        if rank == 0:
+            print("===> Start calculating recalls")
+        recalls = recalls_from_topk_device(idx, ground_truth, pids, recall_topk, nms)
+        if rank == 0:
+            _print_recalls(recalls, recall_topk)
+            print("Applying re-ranking ...")
+        distmat = re_ranking_features(q_feat.contiguous(), g_feat.contiguous(), k1=rr_topk, k2=1,
+                                      lambda_value=lambda_value, precision=prec)
+        if rank == 0:
+            print("===> Start calculating recalls")
+        _, idx = ops.row_topk(distmat, k)
+        recalls = recalls_from_topk_device(idx, ground_truth, pids, recall_topk, nms)
+        if rank == 0:
+            _print_recalls(recalls, recall_topk)
+        return recalls
+
     def evaluate(self, query_loader, dataset, query, gallery, ground_truth, gallery_loader=None,
                  vlad=True, pca=None, rerank=False, gpu=None, sync_gather=False, nms=False,
                  rr_topk=25, lambda_value=0, device_resident=True):
+        if rerank and self.device_rerank:
+            return self._evaluate_device_rerank(query_loader, dataset, query, gallery, ground_truth,
+                                                gallery_loader, vlad, pca, gpu, nms, rr_topk, lambda_value)
         if device_resident and gallery_loader is not None and not rerank:
             return self._evaluate_device(query_loader, query, gallery, ground_truth,
                                          gallery_loader, vlad, pca, gpu, nms)

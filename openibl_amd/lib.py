@@ -61,6 +61,21 @@ SIGNATURES = {
     "oibl_region_vlad_forward": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
                                          c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "oibl_region_scores": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "oibl_rerank_row_extremes_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "oibl_rerank_row_extremes": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "oibl_rerank_set_stride": (c_int, [c_int, c_int]),
+    "oibl_rerank_sets": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p]),
+    "oibl_rerank_weights": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int,
+                                    c_void_p, c_void_p]),
+    "oibl_rerank_expand": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+                                   c_void_p, c_void_p, c_int, c_void_p]),
+    "oibl_rerank_invert_workspace_bytes": (c_size_t, [c_int, c_size_t]),
+    "oibl_rerank_invert": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_size_t, c_void_p, c_void_p,
+                                   c_void_p, c_void_p, c_size_t, c_void_p]),
+    "oibl_rerank_jaccard_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "oibl_rerank_jaccard": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                    c_int, c_int, C.c_float, C.c_float, c_void_p, c_size_t, c_void_p, c_size_t,
+                                    c_void_p]),
     "oibl_pca_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "oibl_pca_forward": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int,
                                  c_void_p, c_void_p, c_size_t, c_void_p]),

@@ -1099,3 +1099,151 @@ def gemm_nt(a: torch.Tensor, b: torch.Tensor, regstage: bool = False) -> torch.T
     _lib.check(_lib.load().oibl_gemm_nt(_ptr(a), M, _ptr(b), N, K, p | (0x100 if regstage else 0),
                                         _ptr(c), N, _stream(dev)), "gemm_nt")
     return c
+
+
+# ---------------------------------------------------------------------------------------------
+# k-reciprocal re-ranking from descriptor rows, one wrapper per stage (csrc/rerank.hip; the
+# stages are put together by openibl_amd.rerank.re_ranking_features)
+# ---------------------------------------------------------------------------------------------
+RERANK_MAX_K1 = 31
+RERANK_MAX_K2 = 8
+
+
+def rerank_half(k1: int) -> int:
+    """round(k1 / 2) as the reference rounds it (np.around: halves to even)."""
+    return int(round(k1 / 2.0))
+
+
+def rerank_check_limits(k1: int, k2: int) -> None:
+    """ValueError for parameters beyond what the kernels are built for (never a silent truncation)."""
+    if int(k1) != k1 or not 1 <= k1 <= RERANK_MAX_K1:
+        raise ValueError(f"re-ranking on the device is built for 1 <= k1 <= {RERANK_MAX_K1} (got k1={k1!r})")
+    if int(k2) != k2 or not 1 <= k2 <= RERANK_MAX_K2:
+        raise ValueError(f"re-ranking on the device is built for 1 <= k2 <= {RERANK_MAX_K2} (got k2={k2!r})")
+
+
+def rerank_set_stride(k1: int, half: Optional[int] = None) -> int:
+    """Slots per item of the set arrays: (k1 + 1)(half + 2), the most members an expanded set can have."""
+    rerank_check_limits(k1, 1)
+    return (k1 + 1) * ((rerank_half(k1) if half is None else int(half)) + 2)
+
+
+def _i32(t: torch.Tensor, what: str) -> None:
+    if t.dtype != torch.int32:
+        raise ValueError(f"{what} must be int32")
+
+
+def rerank_row_extremes(x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """x [n][d] float32 -> (norms [n] = |x_i|^2, rowmax [n] = max_r D[r][i]^2) with D the squared-L2 matrix of x
+    against itself, contracted in fp32 and never written."""
+    dev = _need_cuda(x)
+    if x.dtype != torch.float32 or x.dim() != 2:
+        raise ValueError("rerank_row_extremes expects a float32 [n][d] tensor")
+    n, d = map(int, x.shape)
+    norms = torch.empty((n,), dtype=torch.float32, device=dev)
+    rowmax = torch.empty((n,), dtype=torch.float32, device=dev)
+    if n == 0:
+        return norms, rowmax
+    lib = _lib.load()
+    ws = workspace(lib.oibl_rerank_row_extremes_workspace_bytes(n, d), dev, "rerank")
+    _lib.check(lib.oibl_rerank_row_extremes(_ptr(x), n, d, _ptr(norms), _ptr(rowmax), _ptr(ws), ws.numel(),
+                                            _stream(dev)), "rerank_row_extremes")
+    return norms, rowmax
+
+
+def rerank_sets(rank: torch.Tensor, k1: int, half: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """rank [n][>= k1 + 1] int32 (nearest first, the item itself included) -> (idx [n][stride] int32: the expanded
+    k-reciprocal set of every item, ascending, slots beyond the count undefined; cnt [n] int32)."""
+    rerank_check_limits(k1, 1)
+    dev = _need_cuda(rank)
+    _i32(rank, "rerank_sets: rank")
+    half = rerank_half(k1) if half is None else int(half)
+    n, ld = map(int, rank.shape)
+    stride = rerank_set_stride(k1, half)
+    idx = torch.empty((n, stride), dtype=torch.int32, device=dev)
+    cnt = torch.zeros((n,), dtype=torch.int32, device=dev)
+    if n:
+        _lib.check(_lib.load().oibl_rerank_sets(_ptr(rank), ld, n, int(k1), half, _ptr(idx), _ptr(cnt), stride,
+                                                _stream(dev)), "rerank_sets")
+    return idx, cnt
+
+
+def rerank_weights(x: torch.Tensor, norms: torch.Tensor, rowmax: torch.Tensor, idx: torch.Tensor,
+                   cnt: torch.Tensor) -> torch.Tensor:
+    """val [n][stride] float32: exp(-D[i][c]^2 / rowmax[i]) over the members c of item i, normalised to sum 1."""
+    dev = _need_cuda(x, norms, rowmax, idx, cnt)
+    _i32(idx, "rerank_weights: idx")
+    _i32(cnt, "rerank_weights: cnt")
+    if x.dtype != torch.float32 or norms.dtype != torch.float32 or rowmax.dtype != torch.float32:
+        raise ValueError("rerank_weights expects float32 rows, norms and row maxima")
+    n, d = map(int, x.shape)
+    val = torch.empty(idx.shape, dtype=torch.float32, device=dev)
+    if n:
+        _lib.check(_lib.load().oibl_rerank_weights(_ptr(x), _ptr(norms), _ptr(rowmax), n, d, _ptr(idx), _ptr(cnt),
+                                                   int(idx.shape[1]), _ptr(val), _stream(dev)), "rerank_weights")
+    return val
+
+
+def rerank_expand(rank: torch.Tensor, k2: int, idx: torch.Tensor, val: torch.Tensor, cnt: torch.Tensor):
+    """The k2 query expansion: (idx2, val2, cnt2) with row i the mean of the sparse rows of the k2 nearest items of
+    i (rank[i][:k2]), stride k2 * stride."""
+    rerank_check_limits(1, k2)
+    dev = _need_cuda(rank, idx, val, cnt)
+    for t, what in ((rank, "rank"), (idx, "idx"), (cnt, "cnt")):
+        _i32(t, "rerank_expand: " + what)
+    n, ld = map(int, rank.shape)
+    stride = int(idx.shape[1])
+    stride2 = int(k2) * stride
+    idx2 = torch.empty((n, stride2), dtype=torch.int32, device=dev)
+    val2 = torch.empty((n, stride2), dtype=torch.float32, device=dev)
+    cnt2 = torch.zeros((n,), dtype=torch.int32, device=dev)
+    if n:
+        _lib.check(_lib.load().oibl_rerank_expand(_ptr(rank), ld, n, int(k2), _ptr(idx), _ptr(val), _ptr(cnt), stride,
+                                                  _ptr(idx2), _ptr(val2), _ptr(cnt2), stride2, _stream(dev)),
+                   "rerank_expand")
+    return idx2, val2, cnt2
+
+
+def rerank_invert(idx: torch.Tensor, val: torch.Tensor, cnt: torch.Tensor):
+    """The inverted index of the sparse rows: (col_off [n + 1] int32, inv_row [nnz] int32, inv_val [nnz] float32) —
+    column c is held by rows inv_row[col_off[c]:col_off[c + 1]], ascending.  Reads the total count back (one
+    integer) to size the outputs."""
+    dev = _need_cuda(idx, val, cnt)
+    _i32(idx, "rerank_invert: idx")
+    _i32(cnt, "rerank_invert: cnt")
+    n, stride = map(int, idx.shape)
+    nnz = int(cnt.sum(dtype=torch.int64).item()) if n else 0
+    col_off = torch.zeros((n + 1,), dtype=torch.int32, device=dev)
+    inv_row = torch.empty((max(nnz, 1),), dtype=torch.int32, device=dev)
+    inv_val = torch.empty((max(nnz, 1),), dtype=torch.float32, device=dev)
+    if n:
+        lib = _lib.load()
+        ws = workspace(lib.oibl_rerank_invert_workspace_bytes(n, nnz), dev, "rerank")
+        _lib.check(lib.oibl_rerank_invert(_ptr(idx), _ptr(val), _ptr(cnt), stride, n, nnz, _ptr(col_off),
+                                          _ptr(inv_row), _ptr(inv_val), _ptr(ws), ws.numel(), _stream(dev)),
+                   "rerank_invert")
+    return col_off, inv_row[:nnz], inv_val[:nnz]
+
+
+def rerank_jaccard(idx: torch.Tensor, val: torch.Tensor, cnt: torch.Tensor, col_off: torch.Tensor,
+                   inv_row: torch.Tensor, inv_val: torch.Tensor, rowmax: torch.Tensor, dist: torch.Tensor,
+                   lambda_value: float) -> torch.Tensor:
+    """dist [Q][G] float32 holds the squared distances of the query rows (items 0..Q-1) to the gallery rows (items
+    Q..Q+G-1); it is overwritten with (1 - lambda) * jaccard + lambda * dist^2 / rowmax[i] and returned."""
+    dev = _need_cuda(idx, val, cnt, col_off, inv_row, inv_val, rowmax, dist)
+    if dist.dtype != torch.float32 or dist.dim() != 2:
+        raise ValueError("rerank_jaccard: dist must be a float32 [Q][G] matrix")
+    Q, G = map(int, dist.shape)
+    if Q + G != int(cnt.shape[0]):
+        raise ValueError("rerank_jaccard: dist must be [Q][G] with Q + G = the number of items")
+    if Q == 0 or G == 0:
+        return dist
+    import numpy as _np
+    lam = float(_np.float32(lambda_value))
+    oml = float(_np.float32(1.0 - lambda_value))
+    lib = _lib.load()
+    ws = workspace(lib.oibl_rerank_jaccard_workspace_bytes(Q, G), dev, "rerank")
+    _lib.check(lib.oibl_rerank_jaccard(_ptr(idx), _ptr(val), _ptr(cnt), int(idx.shape[1]), _ptr(col_off),
+                                       _ptr(inv_row), _ptr(inv_val), _ptr(rowmax), Q, G, oml, lam, _ptr(dist),
+                                       int(dist.stride(0)), _ptr(ws), ws.numel(), _stream(dev)), "rerank_jaccard")
+    return dist
