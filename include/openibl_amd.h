@@ -562,6 +562,30 @@ int oibl_rerank_jaccard(const int32_t* idx, const float* val, const int32_t* cnt
 int oibl_cluster_means(const float* x, const int32_t* labels, int n, int d, int num_clusters,
                        float* centers, int32_t* counts, void* stream);
 
+/* ---- NetVLAD initialisation without a checkpoint ------------------------------------- *
+ * The device pieces around the k-means above (examples/cluster.py:93-104, ibl/models/netvlad.py:34-42).
+ *
+ * oibl_local_descriptors: the sampled, channel-normalised local descriptors of a batch of conv5 maps.
+ *   feat [N][P][C] (NHWC, P = h * w) in `precision` OIBL_BF16 or OIBL_F32; positions [N][S] int32 in [0, P);
+ *   out [N*S][C] fp32: row n * S + s = feat[n][positions[n][s]][:] / max(|.|_2, 1e-12)  (F.normalize, then the
+ *   gather).  Only the N * S sampled pixels are read.  C % 64 == 0.  The caller guarantees the range of the
+ *   positions (they live on the device: the host mirror checks them before the launch); a position outside
+ *   [0, P) is not dereferenced, its row is written as NaN.
+ *
+ * oibl_assign_gap: descs [n][C] fp32, clsts [K][C] fp32 ->
+ *   clsts_assign [K][C] = clsts / |clsts|   (row-wise),
+ *   gap [n]             = largest minus second largest of the K products <clsts_assign[k], descs[i]>; the top pair
+ *                         is chosen by cluster INDEX: two identical centres on top give exactly 0,
+ *   *gap_sum (double)   = sum of gap[] in a fixed order that depends on the indices alone.
+ *   alpha of NetVLAD._init_params is -ln(0.01) / (*gap_sum / n).  n >= 1, 2 <= K <= 256, C % 64 == 0.  Exact fp32
+ *   FMA, no atomics: bit-identical results from run to run.  No [K][n] matrix is formed; the workspace holds one
+ *   transposed copy of clsts_assign.  ws 256-byte aligned, gap_sum 8-byte aligned.                             */
+int oibl_local_descriptors(const void* feat, int N, int P, int C, int precision, const int32_t* positions, int S,
+                           float* out, void* stream);
+size_t oibl_assign_gap_workspace_bytes(int n, int K, int C);
+int oibl_assign_gap(const float* descs, int n, const float* clsts, int K, int C, float* clsts_assign, float* gap,
+                    double* gap_sum, void* ws, size_t ws_bytes, void* stream);
+
 /* n 32-bit words src -> dst, by a kernel (one workgroup) on `stream`: dst may be pinned (host-coherent)
  * memory mapped into the device — how the f16mx range flag reaches the host behind a replayed graph without a
  * DMA-engine copy that would queue behind the next batch's input transfer. */

@@ -23,14 +23,28 @@ step:
 scikit-learn accumulates the means in float32 in thread-dependent chunks; here they are correctly
 rounded, so centres agree to ~1e-6 relative, not bit for bit (tests/golden/kmeans.npz, produced by
 the reference's own call).  `assign_fn` / `update_fn` are injection points for the CPU tests.
+
+Around the k-means, the rest of the reference's initialisation flow (README "Initialising NetVLAD without a
+checkpoint"):
+
+  * `sample_positions` / `sample_local_descriptors`   examples/cluster.py:93-104: 100 random positions of the
+    channel-normalised conv5 map per image (`oibl_local_descriptors` reads only those), with numpy's draws in
+    the reference's order — the same seed picks the same positions;
+  * `build_init_cache` / `load_init_cache`            the `<arch>_<dataset>_<K>_desc_cen.hdf5` file (datasets
+    `descriptors`, `centroids`) that carries both to the training scripts;
+  * `netvlad_init`                                    ibl/models/netvlad.py:34-42: alpha, centroids and the
+    assignment weights from the centres and the descriptors (`oibl_assign_gap`); `NetVLAD._init_params()` is
+    this function plus the three writes.
 """
 from __future__ import annotations
 
-from typing import Callable, Optional, Tuple
+import math
+from typing import Callable, Iterable, Optional, Tuple
 
 import numpy as np
 
-__all__ = ["kmeans_centroids"]
+__all__ = ["kmeans_centroids", "sample_positions", "sample_local_descriptors", "netvlad_init",
+           "build_init_cache", "load_init_cache"]
 
 
 def _hip_assign(x_dev, centers: np.ndarray):
@@ -114,3 +128,118 @@ def kmeans_centroids(descriptors, num_clusters: int = 64, max_iter: int = 100, s
         labels_old = labels
     out = (centers + x_mean).astype(np.float32)
     return (out, n_iter) if return_n_iter else out
+
+
+# ---- local descriptors (examples/cluster.py:93-104) ------------------------------------------------------------
+def sample_positions(n_images: int, P: int, n_per_image: int, rng=np.random) -> np.ndarray:
+    """int64 [n_images][n_per_image]: `rng.choice(P, n_per_image, replace=False)` once per image, in image order —
+    the draws of examples/cluster.py:100-102, so the same seed picks the same positions.  n_per_image > P raises
+    ValueError, as numpy does."""
+    if n_per_image > P:
+        raise ValueError(f"Cannot take a larger sample ({n_per_image}) than population ({P}) when 'replace=False'")
+    out = np.empty((int(n_images), int(n_per_image)), dtype=np.int64)
+    for i in range(int(n_images)):
+        out[i] = rng.choice(P, n_per_image, replace=False)
+    return out
+
+
+def _hip_gather(feat, positions):
+    from . import ops
+    return ops.local_descriptors(feat, positions)
+
+
+def sample_local_descriptors(model, batches: Iterable, n_descriptors: int = 50000, n_per_image: int = 100,
+                             rng=np.random, gather_fn: Optional[Callable] = None):
+    """The `descriptors` dataset of examples/cluster.py: float32 device tensor [n_descriptors][C], rows
+    batchix + ix * n_per_image .. + n_per_image of it the sampled, L2-normalised conv5 descriptors of image ix of
+    a batch.  `model` is a VGG or anything with a `base_model`; `batches` yields image tensors or the reference
+    loader's 5-tuples (image first).  Each batch goes through `features_nhwc` — no NCHW copy of the map, and only
+    the sampled pixels are normalised — with the f16mx range flag settled behind the gather (a flagged batch is
+    gathered again from its bf16x3 map, as models._with_range_guard does).  ceil(n_descriptors / n_per_image)
+    images are used; a RuntimeError says so when `batches` ends before that.  `gather_fn(feat, positions)` is the
+    injection point of the CPU tests."""
+    import torch
+    base = getattr(model, "base_model", model)
+    gather = gather_fn or _hip_gather
+    n_images = math.ceil(n_descriptors / n_per_image)
+    params = list(base.parameters()) if hasattr(base, "parameters") else []
+    dev = params[0].device if params else None
+    out, done = None, 0                       # images done
+    for batch in batches:
+        if done >= n_images:
+            break
+        x = batch[0] if isinstance(batch, (tuple, list)) else batch
+        x = x[: n_images - done]
+        if dev is not None:
+            x = x.to(dev)
+        feat = base.features_nhwc(x, defer_flag=True)
+        P = feat.numel() // (int(feat.shape[0]) * int(feat.shape[-1]))
+        pos = sample_positions(int(feat.shape[0]), P, n_per_image, rng)
+        rows = gather(feat, pos)
+        fb = base.settle_range_flag(x)
+        if fb is not None:
+            rows = gather(fb, pos)
+        if out is None:
+            out = torch.empty((n_descriptors, int(rows.shape[1])), dtype=torch.float32, device=rows.device)
+        start = done * n_per_image
+        take = min(int(rows.shape[0]), n_descriptors - start)
+        out[start:start + take] = rows[:take]
+        done += int(feat.shape[0])
+    if done < n_images:
+        raise RuntimeError(f"sample_local_descriptors: {n_descriptors} descriptors at {n_per_image} per image need "
+                           f"{n_images} images, the batches held {done}")
+    return out
+
+
+# ---- NetVLAD._init_params (ibl/models/netvlad.py:34-42) --------------------------------------------------------
+def netvlad_init(clsts, traindescs, device=None):
+    """(alpha, centroids [K][C], conv_weight [K][C][1][1]) from the k-means centres `clsts` [K][C] and the training
+    descriptors `traindescs` [n][C] (numpy or torch): clsts_assign = clsts / |clsts|, per descriptor the gap between
+    its best and second-best product with clsts_assign (`ops.assign_gap`), alpha = -log(0.01) / mean gap in float64
+    on the host, centroids = clsts, conv_weight = alpha * clsts_assign.  Tensors are float32 on the device."""
+    import torch
+    from . import ops
+
+    def to_dev(a):
+        t = a.detach() if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))
+        dev = device
+        if dev is None:
+            dev = t.device if t.is_cuda else torch.device("cuda", torch.cuda.current_device())
+        return t.to(device=dev, dtype=torch.float32).contiguous()
+
+    if not torch.cuda.is_available():
+        from .lib import OpenIBLAmdError
+        raise OpenIBLAmdError("openibl_amd: netvlad_init runs only on an AMD GPU through the HIP extension "
+                              "(there is no CPU fallback)")
+    c, d = to_dev(clsts), to_dev(traindescs)
+    if c.dim() != 2 or d.dim() != 2 or c.shape[1] != d.shape[1]:
+        raise ValueError(f"netvlad_init: clsts [K][C] and traindescs [n][C], got {tuple(c.shape)} and {tuple(d.shape)}")
+    if d.device != c.device:
+        d = d.to(c.device)
+    clsts_assign, _, mean_gap = ops.assign_gap(d, c)
+    alpha = float(-np.log(0.01) / np.float64(mean_gap))
+    conv_weight = (clsts_assign * alpha).reshape(c.shape[0], c.shape[1], 1, 1)
+    return alpha, c, conv_weight
+
+
+# ---- the cache file between the two (examples/cluster.py:84-115, netvlad_img.py:90-95) -------------------------
+def build_init_cache(model, batches: Iterable, path: str, num_clusters: int = 64, seed: int = 43,
+                     max_iter: int = 100, n_descriptors: int = 50000, n_per_image: int = 100, rng=np.random,
+                     gather_fn: Optional[Callable] = None, **kmeans_kwargs) -> str:
+    """examples/cluster.py's main: sample the local descriptors, run `kmeans_centroids` on them and write the cache
+    file `path` (the reference names it <arch>_<dataset>_<K>_desc_cen.hdf5) with the datasets `descriptors`
+    [n_descriptors][C] and `centroids` [num_clusters][C].  HDF5 when h5py is importable, else an npz archive at the
+    same path (the convention of openibl_amd.pca); `load_init_cache` reads both.  Returns the path."""
+    from .pca import _write_arrays
+    descs = sample_local_descriptors(model, batches, n_descriptors, n_per_image, rng=rng, gather_fn=gather_fn)
+    centroids = kmeans_centroids(descs, num_clusters=num_clusters, max_iter=max_iter, seed=seed, **kmeans_kwargs)
+    return _write_arrays(path, descriptors=descs.detach().cpu().numpy(), centroids=centroids)
+
+
+def load_init_cache(path: str) -> Tuple[np.ndarray, np.ndarray]:
+    """(clsts, traindescs) = the `centroids` and `descriptors` datasets of a cache file, as the reference's
+    scripts read them (examples/netvlad_img.py:93-95):
+        model.net_vlad.clsts, model.net_vlad.traindescs = load_init_cache(path); model._init_params()"""
+    from .pca import _read_arrays
+    descs, cents = _read_arrays(path, ("descriptors", "centroids"), what="load_init_cache")
+    return np.asarray(cents, dtype=np.float32), np.asarray(descs, dtype=np.float32)

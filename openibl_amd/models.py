@@ -11,8 +11,9 @@ DDP-saved (`module.`-prefixed) checkpoints load unchanged.  The modules only *ow
     EmbedNet.forward     -> backbone + NetVLAD + norms      (netvlad.py:73-82)
     EmbedNetPCA.forward  -> ... + oibl_pca_forward           (netvlad.py:95-110)
 
-Inference only (the reference's training paths are out of scope).  Inputs must be
-CUDA(HIP) tensors; there is no CPU path.
+Inference only (the reference's training paths are out of scope; `NetVLAD._init_params`, the
+gradient-free initialisation from k-means centres, is here: oibl_assign_gap).  Inputs must be CUDA(HIP)
+tensors; there is no CPU path.
 """
 from __future__ import annotations
 
@@ -320,8 +321,30 @@ class NetVLAD(_PrecisionMixin, nn.Module):
         self._hook_state_dict_loads()
 
     def _init_params(self):
-        raise NotImplementedError("NetVLAD._init_params (k-means initialisation for training) is "
-                                  "outside the inference path this package implements")
+        """ibl/models/netvlad.py:34-42: alpha, centroids and conv.weight from the k-means centres `self.clsts`
+        [K][C] and the training descriptors `self.traindescs` [n][C] (numpy arrays or tensors; see
+        openibl_amd.cluster for where they come from).  The arithmetic runs on the HIP device — the module's own
+        if its parameters are there, else the current one: the reference's scripts call this before .cuda() —
+        and the results are written through `.data.copy_` as the reference does; the packed parameter copies
+        and captured forwards are told (invalidate())."""
+        for name in ("clsts", "traindescs"):
+            if getattr(self, name) is None:
+                raise ValueError(f"NetVLAD._init_params: `{name}` is not set (the k-means centres and the sampled "
+                                 f"training descriptors: openibl_amd.cluster.load_init_cache)")
+        if tuple(self.clsts.shape) != (self.num_clusters, self.dim):
+            raise ValueError(f"NetVLAD._init_params: clsts is {tuple(self.clsts.shape)}, the layer holds "
+                             f"{self.num_clusters} clusters of dimension {self.dim}")
+        if not torch.cuda.is_available():
+            raise ops._lib.OpenIBLAmdError("openibl_amd: NetVLAD._init_params runs only on an AMD GPU through the "
+                                           "HIP extension (there is no CPU fallback)")
+        from .cluster import netvlad_init
+        own = self.centroids.device
+        dev = own if own.type == "cuda" else torch.device("cuda", torch.cuda.current_device())
+        alpha, centroids, conv_weight = netvlad_init(self.clsts, self.traindescs, device=dev)
+        self.alpha = alpha
+        self.centroids.data.copy_(centroids)
+        self.conv.weight.data.copy_(conv_weight)
+        self.invalidate()
 
     def _params(self):
         w = self.conv.weight.detach().float().reshape(self.num_clusters, self.dim).contiguous()

@@ -879,6 +879,59 @@ def cluster_means(x: torch.Tensor, labels: torch.Tensor, centers: torch.Tensor) 
     return counts
 
 
+# ---- NetVLAD initialisation without a checkpoint ----------------------------------------------------
+def local_descriptors(feat_nhwc: torch.Tensor, positions) -> torch.Tensor:
+    """feat [N][h][w][C] (or [N][P][C]) bf16 / fp32, positions [N][S] integers in [0, P) (numpy or torch, host or
+    device) -> [N*S][C] fp32: row n*S + s = F.normalize(feat[n, positions[n, s], :]) (examples/cluster.py:97-104;
+    oibl_local_descriptors).  Only the sampled pixels are read.  The range of the positions is checked on the host
+    BEFORE anything is launched (ValueError)."""
+    dev = _need_cuda(feat_nhwc)
+    if feat_nhwc.dim() not in (3, 4) or feat_nhwc.dtype not in (torch.bfloat16, torch.float32):
+        raise ValueError("local_descriptors: feature map must be a bf16 or fp32 [N][h][w][C] / [N][P][C] tensor")
+    N, C_ = int(feat_nhwc.shape[0]), int(feat_nhwc.shape[-1])
+    if N == 0 or C_ == 0 or C_ % 64:
+        raise ValueError(f"local_descriptors: {N} images of {C_} channels (C must be a positive multiple of 64)")
+    P = feat_nhwc.numel() // (N * C_)
+    pos = positions.detach().cpu() if torch.is_tensor(positions) else torch.as_tensor(positions)
+    if pos.dim() != 2 or int(pos.shape[0]) != N or int(pos.shape[1]) == 0 or pos.is_floating_point() \
+            or pos.dtype == torch.bool:
+        raise ValueError(f"local_descriptors: positions must be integers [N = {N}][S >= 1], got {tuple(pos.shape)} "
+                         f"{pos.dtype}")
+    lo, hi = int(pos.min()), int(pos.max())
+    if lo < 0 or hi >= P:
+        raise ValueError(f"local_descriptors: positions must lie in [0, {P}) (got {lo} .. {hi})")
+    S = int(pos.shape[1])
+    pos_dev = pos.to(torch.int32).contiguous().to(dev)
+    out = torch.empty((N * S, C_), dtype=torch.float32, device=dev)
+    p = BF16 if feat_nhwc.dtype == torch.bfloat16 else F32
+    _lib.check(_lib.load().oibl_local_descriptors(_ptr(feat_nhwc), N, P, C_, p, _ptr(pos_dev), S, _ptr(out),
+                                                  _stream(dev)), "local_descriptors")
+    return out
+
+
+def assign_gap(descs: torch.Tensor, clsts: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, float]:
+    """descs [n][C], clsts [K][C] fp32 -> (clsts_assign [K][C] = clsts / |clsts|, gap [n] = best minus second best
+    of the K products clsts_assign . desc, mean gap as a Python float = gap_sum / n in double): the arithmetic of
+    NetVLAD._init_params (ibl/models/netvlad.py:35-40; oibl_assign_gap), without its [K][n] matrix.  Reading the
+    mean synchronises with the stream."""
+    dev = _need_cuda(descs, clsts)
+    if descs.dtype != torch.float32 or clsts.dtype != torch.float32 or descs.dim() != 2 or clsts.dim() != 2 \
+            or descs.shape[1] != clsts.shape[1]:
+        raise ValueError("assign_gap expects contiguous float32 descs [n][C] and clsts [K][C]")
+    n, C_, K = int(descs.shape[0]), int(descs.shape[1]), int(clsts.shape[0])
+    if n < 1 or K < 2 or K > 256 or C_ == 0 or C_ % 64:
+        raise ValueError(f"assign_gap: n = {n}, K = {K}, C = {C_}: needs n >= 1, 2 <= K <= 256 and C a positive "
+                         f"multiple of 64")
+    lib = _lib.load()
+    ws = workspace(lib.oibl_assign_gap_workspace_bytes(n, K, C_), dev, "assign_gap")
+    clsts_assign = torch.empty((K, C_), dtype=torch.float32, device=dev)
+    gap = torch.empty((n,), dtype=torch.float32, device=dev)
+    gap_sum = torch.empty((1,), dtype=torch.float64, device=dev)
+    _lib.check(lib.oibl_assign_gap(_ptr(descs), n, _ptr(clsts), K, C_, _ptr(clsts_assign), _ptr(gap), _ptr(gap_sum),
+                                   _ptr(ws), ws.numel(), _stream(dev)), "assign_gap")
+    return clsts_assign, gap, float(gap_sum.item()) / n
+
+
 class PreparedRows:
     """A descriptor matrix ready for matching in one precision: the rows the contraction reads and
     their fp32 squared norms (oibl_match_prepare).  Build it once for a matrix that is matched many

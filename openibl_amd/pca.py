@@ -31,29 +31,29 @@ def _rank() -> int:
 _HDF5_MAGIC = b"\x89HDF\r\n\x1a\n"
 
 
-def _read_params(path: str):
-    """(U, lams, mu, Utmu) from the reference's HDF5 file or from an npz archive holding the same
-    four arrays.  The format is sniffed from the file's first bytes, not from its name: without
-    h5py `train` writes the archive AT the path the caller chose (examples/test.py:109-111 decides
-    with osp.isfile(<...>.h5) whether to train again)."""
-    if not os.path.exists(path) and os.path.exists(path + ".npz"):
-        path = path + ".npz"                   # files written by earlier versions of this package
+def _read_arrays(path: str, names, what: str = "PCA.load"):
+    """The datasets `names` of an HDF5 file, or of an npz archive holding arrays of the same names.
+    The format is sniffed from the file's first bytes, not from its name: without h5py the writers
+    put the archive AT the path the caller chose (examples/test.py:109-111 decides with
+    osp.isfile(<...>.h5) whether to train again).  Also serves the NetVLAD initialisation cache
+    (openibl_amd.cluster)."""
     with open(path, "rb") as f:
         magic = f.read(8)
     if magic != _HDF5_MAGIC:
         z = np.load(path)
-        return z["U"], z["lams"], z["mu"], z["Utmu"]
+        return tuple(z[k] for k in names)
     try:
         import h5py
     except ImportError as e:
-        raise ImportError(f"PCA.load: {path} is an HDF5 file and h5py is not installed (an npz "
-                          "archive with the arrays U, lams, mu, Utmu at the same path is accepted "
+        raise ImportError(f"{what}: {path} is an HDF5 file and h5py is not installed (an npz "
+                          f"archive with the arrays {', '.join(names)} at the same path is accepted "
                           "as well)") from e
     with h5py.File(path, "r") as f:
-        return f["U"][...], f["lams"][...], f["mu"][...], f["Utmu"][...]
+        return tuple(f[k][...] for k in names)
 
 
-def _write_params(path: str, U, lams, mu, Utmu) -> str:
+def _write_arrays(path: str, **arrays) -> str:
+    """HDF5 datasets when h5py is importable, else the same arrays in an npz container at the SAME path."""
     folder = os.path.dirname(path)
     if folder:
         os.makedirs(folder, exist_ok=True)
@@ -62,12 +62,24 @@ def _write_params(path: str, U, lams, mu, Utmu) -> str:
         if not hasattr(h5py, "File"):
             raise ImportError
         with h5py.File(path, "w") as f:
-            for k, v in (("U", U), ("lams", lams), ("mu", mu), ("Utmu", Utmu)):
+            for k, v in arrays.items():
                 f.create_dataset(k, data=v)
     except ImportError:
-        with open(path, "wb") as f:            # same four arrays, npz container, SAME path
-            np.savez(f, U=U, lams=lams, mu=mu, Utmu=Utmu)
+        with open(path, "wb") as f:
+            np.savez(f, **arrays)
     return path
+
+
+def _read_params(path: str):
+    """(U, lams, mu, Utmu) from the reference's HDF5 file or from an npz archive holding the same
+    four arrays."""
+    if not os.path.exists(path) and os.path.exists(path + ".npz"):
+        path = path + ".npz"                   # files written by earlier versions of this package
+    return _read_arrays(path, ("U", "lams", "mu", "Utmu"))
+
+
+def _write_params(path: str, U, lams, mu, Utmu) -> str:
+    return _write_arrays(path, U=U, lams=lams, mu=mu, Utmu=Utmu)
 
 
 class PCA:
