@@ -307,6 +307,29 @@ int oibl_region_vlad_forward(const void* feat, int N, int h, int w, int K, int C
                              float* region_vlad, void* ws, size_t ws_bytes, void* stream);
 int oibl_region_scores(const float* region_vlad, int T, int per_tuple, int L, float* score, void* stream);
 
+/* ---- NetVLAD + intra-norm + L2: gradients ------------------------------------------- *
+ * The backward of oibl_netvlad_forward's vlad_norm, i.e. of NetVLAD.forward (ibl/models/netvlad.py:44-61) followed
+ * by the two F.normalize calls of EmbedNet.forward (netvlad.py:78-80), as torch autograd differentiates them (a
+ * norm clamped at eps = 1e-12 is a constant denominator).  Stateless: nothing is carried over from a forward call,
+ * the per-pixel norms, the soft-assignment and the aggregated rows are recomputed from `feat`.
+ * feat [N][P][C] fp32 (precision must be OIBL_F32), assign_w / centroids [K][C] fp32, K = 64 and C = 512 only;
+ * grad_vlad_norm [N][K*C] fp32, k-major: dL/d vlad_norm.  Outputs, each optional (may be NULL, at least one is
+ * needed), OVERWRITTEN, not accumulated into:
+ *   grad_assign_w  [K][C]     dL/d conv.weight[:, :, 0, 0], summed over the images in image order
+ *   grad_centroids [K][C]     dL/d centroids, summed over the images in image order
+ *   grad_feat      [N][P][C]  dL/d feat; with NULL here that stage is not launched.
+ * No floating-point atomics: results are bit-identical from run to run, an output does not depend on which other
+ * outputs are requested, and the grad_feat rows of an image do not depend on its batch mates.
+ * Workspace from oibl_netvlad_backward_workspace_bytes (linear in N, smaller without grad_feat; 0 for an invalid
+ * shape), 256-byte aligned; the other pointers 16-byte aligned.  Invalid arguments (a null input, no output, K != 64,
+ * C != 512, another precision, N or P < 1, N > 65535: the image index is a grid dimension) return OIBL_E_INVALID, a short or misaligned workspace OIBL_E_WORKSPACE;
+ * nothing is launched then.                                                                                        */
+size_t oibl_netvlad_backward_workspace_bytes(int N, int P, int K, int C, int want_grad_feat);
+int oibl_netvlad_backward(const void* feat, int N, int P, int K, int C, int precision,
+                          const float* assign_w, const float* centroids, int normalize_input,
+                          const float* grad_vlad_norm, float* grad_assign_w, float* grad_centroids,
+                          float* grad_feat, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- PCA-whitening projection + L2 ------------------------------------------------ *
  * Replaces EmbedNetPCA.pca_layer + F.normalize (netvlad.py:105-108) and PCA.infer
  * (ibl/pca.py:108-123):  y = normalize(W v + b).

@@ -57,6 +57,9 @@ SIGNATURES = {
     "oibl_netvlad_forward": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p,
                                      c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_size_t,
                                      c_void_p]),
+    "oibl_netvlad_backward_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "oibl_netvlad_backward": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int,
+                                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "oibl_region_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "oibl_region_vlad_forward": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
                                          c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),

@@ -354,6 +354,13 @@ class NetVLAD(_PrecisionMixin, nn.Module):
         w, c = self._params()
         return ops.netvlad(feat, w, c, self.normalize_input, want_raw=want_raw, want_norm=want_norm)
 
+    def head_with_grad(self, feat_nhwc: torch.Tensor) -> torch.Tensor:
+        """conv5_3 map (NHWC, fp32; bf16 is widened) -> vlad [N][K*C], intra- and L2-normalised, bit-equal to
+        `aggregate_nhwc(feat, want_norm=True)` on an fp32 map and carrying an autograd graph to the LIVE
+        `conv.weight` and `centroids` (and to the map, if it requires a gradient): netvlad.py:44-61 + 78-80 with
+        their backward on the device (ops.netvlad_head)."""
+        return ops.netvlad_head(feat_nhwc, self.conv.weight, self.centroids, self.normalize_input)
+
     @torch.no_grad()
     def forward(self, x):
         """x: the backbone's [N][C][h][w] fp32 map (reference layout)."""
@@ -381,6 +388,27 @@ class EmbedNet(_PrecisionMixin, nn.Module):
     @torch.no_grad()
     def forward(self, x):
         return _with_range_guard(self.base_model, x, self._head)
+
+    def forward_train(self, x):
+        """(pool_x [N][512], vlad_x [N][K*C]) as `forward`, with vlad_x carrying an autograd graph to
+        `net_vlad.conv.weight` and `net_vlad.centroids`: the "train only the VLAD layer" setting, for any loss
+        written in torch and any torch optimizer.  The backbone is FROZEN here: it runs under no_grad in the model's
+        precision, through the same range-guarded path as the eval forward, and its parameters receive no gradient
+        (pool_x carries no graph either).  The parameters are read live, so the eval forward after an
+        `optimizer.step()` sees the stepped weights.  vlad_x is bit-equal to the eval forward's where the conv5 map
+        is fp32 (fp32, f16mx, bf16x3); in bf16 the map is widened to fp32 and the fp32 head runs on it, so the bits
+        differ from the eval forward's bf16 head.  Unlike the eval forward, which reads the f16mx range flag behind
+        the head's launches, this one reads it — a host synchronisation — BEFORE the head is enqueued: the autograd
+        graph must be built on the map that stands."""
+        maps = []
+
+        def keep(feat):
+            maps.append(feat)
+            return ops.global_maxpool_nhwc(feat)
+
+        with torch.no_grad():
+            pool_x = _with_range_guard(self.base_model, x, keep)
+        return pool_x, self.net_vlad.head_with_grad(maps[-1])
 
 
 class EmbedNetPCA(_PrecisionMixin, nn.Module):

@@ -489,6 +489,71 @@ def netvlad(feat: torch.Tensor, assign_w: torch.Tensor, centroids: torch.Tensor,
     return raw, nrm
 
 
+def netvlad_backward(feat: torch.Tensor, assign_w: torch.Tensor, centroids: torch.Tensor, grad_out: torch.Tensor,
+                     normalize_input: bool = True, want: Sequence[str] = ("w", "c", "x")):
+    """Gradients of `netvlad(...)`'s vlad_norm (NetVLAD.forward + the two normalisations of EmbedNet.forward,
+    ibl/models/netvlad.py:44-61, 78-80; oibl_netvlad_backward).  feat [N][h][w][C] (or [N][P][C]) fp32, grad_out
+    [N][K*C] fp32 = dL/d vlad_norm -> (grad_assign_w [K][C] | None, grad_centroids [K][C] | None, grad_feat like
+    feat | None) for the letters in `want` ("w", "c", "x").  Stateless: the forward's intermediates are recomputed
+    from feat.  Bit-identical from run to run; an output does not depend on which others are asked for."""
+    dev = _need_cuda(feat, assign_w, centroids, grad_out)
+    want = tuple(want)
+    if not want or any(t not in ("w", "c", "x") for t in want):
+        raise ValueError(f"netvlad_backward: want must name some of 'w', 'c', 'x' (got {want!r})")
+    if feat.dtype != torch.float32 or grad_out.dtype != torch.float32:
+        raise ValueError("netvlad_backward: feature map and grad_out must be fp32")
+    N, C_ = int(feat.shape[0]), int(feat.shape[-1])
+    P = feat.numel() // (N * C_)
+    K = int(centroids.shape[0])
+    aw = assign_w.reshape(K, C_)
+    if aw.dtype != torch.float32 or centroids.dtype != torch.float32 or not aw.is_contiguous():
+        raise ValueError("netvlad_backward: assign_w / centroids must be contiguous float32")
+    if grad_out.numel() != N * K * C_:
+        raise ValueError(f"netvlad_backward: grad_out has {grad_out.numel()} elements, expected {N} x {K * C_}")
+    lib = _lib.load()
+    ws = workspace(lib.oibl_netvlad_backward_workspace_bytes(N, P, K, C_, int("x" in want)), dev, "netvlad_backward")
+    gw = torch.empty((K, C_), dtype=torch.float32, device=dev) if "w" in want else None
+    gc = torch.empty((K, C_), dtype=torch.float32, device=dev) if "c" in want else None
+    gx = torch.empty(feat.shape, dtype=torch.float32, device=dev) if "x" in want else None
+    _lib.check(lib.oibl_netvlad_backward(_ptr(feat), N, P, K, C_, F32, _ptr(aw), _ptr(centroids),
+                                         int(normalize_input), _ptr(grad_out), _ptr(gw), _ptr(gc), _ptr(gx),
+                                         _ptr(ws), ws.numel(), _stream(dev)), "netvlad_backward")
+    return gw, gc, gx
+
+
+class _NetVLADHead(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, feat, assign_w, centroids, normalize_input):
+        ctx.save_for_backward(feat, assign_w, centroids)
+        ctx.normalize_input = bool(normalize_input)
+        return netvlad(feat, assign_w, centroids, normalize_input=ctx.normalize_input, want_norm=True)[1]
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        feat, assign_w, centroids = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        want = tuple(t for t, n in zip(("x", "w", "c"), need[:3]) if n)
+        if not want:
+            return None, None, None, None
+        gw, gc, gx = netvlad_backward(feat, assign_w, centroids, grad_out.contiguous(),
+                                      normalize_input=ctx.normalize_input, want=want)
+        if gw is not None:
+            gw = gw.reshape(assign_w.shape)
+        return gx, gw, gc, None
+
+
+def netvlad_head(feat: torch.Tensor, assign_w: torch.Tensor, centroids: torch.Tensor,
+                 normalize_input: bool = True) -> torch.Tensor:
+    """The differentiable descriptor head: vlad_norm [N][K*C], bit-equal to `netvlad(..., want_norm=True)`, with a
+    graph to whichever of feat, assign_w ([K][C] or conv.weight's [K][C][1][1]) and centroids require a gradient;
+    its backward is one call of `netvlad_backward` for exactly those.  A bf16 map is widened to fp32 first (the
+    gradient kernels are fp32); its gradient then comes back in bf16 through torch's cast."""
+    if feat.dtype == torch.bfloat16:
+        feat = feat.float()
+    _need_cuda(feat, assign_w, centroids)
+    return _NetVLADHead.apply(feat, assign_w, centroids, bool(normalize_input))
+
+
 # ---- SFRS region similarities ---------------------------------------------------------------------
 def region_vlad(feat: torch.Tensor, assign_w: torch.Tensor, centroids: torch.Tensor,
                 normalize_input: bool = True) -> torch.Tensor:
