@@ -273,8 +273,8 @@ __device__ static inline int rr_lower_bound(const int32_t* a, int len, int c) {
 }
 
 // One wave per item: the merge of the sparse rows of its k2 nearest items (itself among them), each value the
-// sum over those rows in rank order divided by k2.  pre_s [k2][stride + 1]: per source row, the number of columns
-// among its first t that no earlier source row holds.
+// sum over those rows in rank order divided by their number (k2, or fewer when the rank list ends in -1).
+// pre_s [k2][stride + 1]: per source row, the number of columns among its first t that no earlier source row holds.
 __global__ __launch_bounds__(64) void rerank_expand_kernel(const int32_t* __restrict__ rank, int ld, int n, int k2,
                                                            const int32_t* __restrict__ idx,
                                                            const float* __restrict__ val,
@@ -286,12 +286,14 @@ __global__ __launch_bounds__(64) void rerank_expand_kernel(const int32_t* __rest
   const int lane = threadIdx.x;
   const int i = blockIdx.x;
   const int P = stride + 1;
+  const int src = lane < k2 ? rank[(size_t)i * ld + lane] : -1;
+  const bool ok = src >= 0 && src < n;
   if (lane < k2) {
-    const int r = rank[(size_t)i * ld + lane];
-    const bool ok = r >= 0 && r < n;
-    row_s[lane] = ok ? r : 0;
-    len_s[lane] = ok ? cnt[r] : 0;
+    row_s[lane] = ok ? src : 0;
+    len_s[lane] = ok ? cnt[src] : 0;
   }
+  // the mean is taken over the items the list holds: n < k2 leaves -1 entries, which np.mean never sees
+  const float fk2 = (float)__builtin_popcountll(__builtin_amdgcn_ballot_w64(ok));
   __syncthreads();
   for (int r = 0; r < k2; ++r) {
     const int32_t* a = idx + (size_t)row_s[r] * stride;
@@ -313,7 +315,6 @@ __global__ __launch_bounds__(64) void rerank_expand_kernel(const int32_t* __rest
     for (int t = 0; t < len_s[lane]; ++t) pr[t + 1] += pr[t];
   }
   __syncthreads();
-  const float fk2 = (float)k2;
   for (int r = 0; r < k2; ++r) {
     const int32_t* a = idx + (size_t)row_s[r] * stride;
     for (int t = lane; t < len_s[r]; t += 64) {
