@@ -267,6 +267,14 @@ int oibl_vgg16_conv5_forward_ev(const float* x_nchw, int N, int H, int W,
                                 const float* const* bias_host, int precision, void* feat,
                                 void* ws, size_t ws_bytes, void* stream, void* ev_igemm_begin,
                                 void* ev_igemm_end);
+/* The frozen trunk of conv5 training: conv1_1 .. conv4_3 + pool exactly as oibl_vgg16_conv5_forward runs them (the
+ * same stems, kernels and — OIBL_F16MX — range flag in the workspace's first word), stopped behind the fourth
+ * max-pool.  Only entries 0..9 of the two pointer arrays are read.  pool4 [N][H/16][W/16][512] is plain fp32 in
+ * activation units in every precision (the stored activation widened: bf16 exactly, bf16x3 hi + lo, f16mx the value
+ * conv5_1 would read with the 1/8 storage scale undone).  Workspace from oibl_vgg16_workspace_bytes.             */
+int oibl_vgg16_pool4_forward(const float* x_nchw, int N, int H, int W, const void* const* packed_w_host,
+                             const float* const* bias_host, int precision, float* pool4,
+                             void* ws, size_t ws_bytes, void* stream);
 
 /* ---- NetVLAD + intra-norm + L2 ---------------------------------------------------- *
  * Replaces NetVLAD.forward (ibl/models/netvlad.py:44-61) and the normalisation that
@@ -329,6 +337,30 @@ int oibl_netvlad_backward(const void* feat, int N, int P, int K, int C, int prec
                           const float* assign_w, const float* centroids, int normalize_input,
                           const float* grad_vlad_norm, float* grad_assign_w, float* grad_centroids,
                           float* grad_feat, void* ws, size_t ws_bytes, void* stream);
+
+/* ---- 3x3 convolution (+ ReLU): gradients -------------------------------------------- *
+ * The backward of nn.Conv2d(Cin, Cout, 3, padding=1) followed by nn.ReLU (ibl/models/vgg.py:41-42, 61-62) as torch
+ * autograd differentiates them: what trains conv5_1 .. conv5_3, the layers the reference's scripts leave unfrozen
+ * (--layers conv5).  Exact fp32 (v_mfma_f32_32x32x2_f32); Cin = Cout = 512 only, every H, W >= 1.
+ * in [N][H][W][Cin] fp32 NHWC, the layer's input; w_oihw [Cout][Cin][3][3] fp32, the state-dict tensor;
+ * out_act NULL or the layer's post-ReLU output [N][H][W][Cout]: grad_out is taken as 0 where out_act <= 0;
+ * grad_out [N][H][W][Cout] fp32: dL/d(output).  With dZ the masked grad_out, the outputs — each optional (may be
+ * NULL, at least one is needed), OVERWRITTEN, not accumulated into; a stage whose output is NULL is not launched:
+ *   grad_w  [Cout][Cin][3][3]  sum over n, y, x of dZ[n][y][x][co] in[n][y+ky-1][x+kx-1][ci], zeros outside the map
+ *   grad_b  [Cout]             sum over n, y, x of dZ[n][y][x][co]
+ *   grad_in [N][H][W][Cin]     the transposed convolution of dZ (taps flipped, Cin / Cout swapped)
+ * The sums over the pixels run in chains of at most 256 products, the chains' results are added in a fixed order
+ * (the last level in fp64, rounded once).  No floating-point atomics: results are bit-identical from run to run, an
+ * output does not depend on which other outputs are requested, and the grad_in rows of an image do not depend on
+ * its batch mates.
+ * Workspace from oibl_conv3x3_backward_workspace_bytes (larger with grad_in; 0 for an invalid shape), 256-byte
+ * aligned; the other pointers 16-byte aligned.  Invalid arguments (a null input, no output, other channel counts,
+ * N, H or W < 1, N*H*W >= 2^31) return OIBL_E_INVALID, a short or misaligned workspace OIBL_E_WORKSPACE; nothing is
+ * launched then.                                                                                                    */
+size_t oibl_conv3x3_backward_workspace_bytes(int N, int H, int W, int cin, int cout, int want_grad_in);
+int oibl_conv3x3_backward(const float* in, int N, int H, int W, int cin, const float* w_oihw, int cout,
+                          const float* out_act, const float* grad_out, float* grad_w, float* grad_b,
+                          float* grad_in, void* ws, size_t ws_bytes, void* stream);
 
 /* ---- PCA-whitening projection + L2 ------------------------------------------------ *
  * Replaces EmbedNetPCA.pca_layer + F.normalize (netvlad.py:105-108) and PCA.infer

@@ -113,12 +113,14 @@ __global__ void mx_pack_rows_kernel(const char* __restrict__ src, char* __restri
 }
 // f16mx lines -> fp32 rows as the kernels see the values: WHICH = 0 hi + q6(lo) (the stored value to
 // ~2^-15), 1 hi alone, 2 q6(hi), 3 q6(lo)   (tests)
-__global__ void mx_join_rows_kernel(const char* __restrict__ src, float* __restrict__ dst, size_t n, int which) {
+// (mul: a power of two that undoes the backbone's storage scale, 1 elsewhere)
+__global__ void mx_join_rows_kernel(const char* __restrict__ src, float* __restrict__ dst, size_t n, int which,
+                                    float mul = 1.f) {
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
        i += (size_t)gridDim.x * blockDim.x) {
     float hi, hi6, lo6;
     mx_line_decode(src + (i >> 5) * 128, (int)(i & 31), hi, hi6, lo6);
-    dst[i] = which == 0 ? hi + lo6 : which == 1 ? hi : which == 2 ? hi6 : lo6;
+    dst[i] = (which == 0 ? hi + lo6 : which == 1 ? hi : which == 2 ? hi6 : lo6) * mul;
   }
 }
 
@@ -3759,7 +3761,7 @@ int oibl_vgg16_conv5_forward(const float* x_nchw, int N, int H, int W,
 static int vgg_forward_impl(const void* x, int u8, const float* mean3, const float* std3, int N, int H,
                             int W, const void* const* packed_w_host, const float* const* bias_host,
                             int precision, void* feat, void* ws, size_t ws_bytes, void* stream,
-                            void* ev_igemm_begin, void* ev_igemm_end) {
+                            void* ev_igemm_begin, void* ev_igemm_end, int last_layer = OIBL_VGG16_NUM_CONV - 1) {
   OIBL_REQUIRE(x && packed_w_host && bias_host && feat && ws, "vgg16: null pointer");
   OIBL_REQUIRE(!u8 || (mean3 && std3), "vgg16: uint8 input needs the mean / std constants");
   OIBL_REQUIRE(precision_ok(precision), "vgg16: bad precision %d", precision);
@@ -3862,10 +3864,12 @@ static int vgg_forward_impl(const void* x, int u8, const float* mean3, const flo
     if (rc) return rc;
     if (ev_igemm_begin) OIBL_HIP_CHECK(hipEventRecord((hipEvent_t)ev_igemm_begin, st));
   }
-  for (int l = l0; l < OIBL_VGG16_NUM_CONV; ++l) {
-    void* dst = (l == OIBL_VGG16_NUM_CONV - 1) ? feat : (l % 2 == 0 ? (void*)bufA : (void*)bufB);
+  for (int l = l0; l <= last_layer; ++l) {
     // bf16x3 / f16mx: the last layer hands the head a plain fp32 map
     const bool last = l == OIBL_VGG16_NUM_CONV - 1;
+    // (a pass that stops at an earlier layer writes `feat` itself only in fp32; the other formats are converted
+    //  behind the loop)
+    void* dst = (last || (l == last_layer && precision == OIBL_F32)) ? feat : (l % 2 == 0 ? (void*)bufA : (void*)bufB);
     rc = conv3x3_impl(cur, N, h, w, kVgg[l].cin, packed_w_host[l], bias_host[l], kVgg[l].cout,
                       kVgg[l].relu, kVgg[l].pool, precision, dst, st, last, splitk, range_flag, act_scale,
                       last ? 1.f / act_scale : 1.f);
@@ -3876,8 +3880,34 @@ static int vgg_forward_impl(const void* x, int u8, const float* mean3, const flo
     }
     cur = dst;
   }
+  if (last_layer != OIBL_VGG16_NUM_CONV - 1 && precision != OIBL_F32) {
+    // the stored activation -> plain fp32 in activation units (f16mx: what the next layer would read, hi + q6(lo),
+    // times the inverse of the storage scale)
+    const size_t n = (size_t)N * h * w * kVgg[last_layer].cout;
+    const unsigned blocks = (unsigned)((n + 255) / 256 > 8192 ? 8192 : (n + 255) / 256);
+    if (precision == OIBL_BF16) {
+      rc = oibl_cast_bf16_to_f32((const uint16_t*)cur, (float*)feat, n, stream);
+      if (rc) return rc;
+    } else if (precision == OIBL_BF16X3) {
+      hipLaunchKernelGGL(x3_join_rows_kernel, dim3(blocks), dim3(256), 0, st, (const char*)cur, (float*)feat, n,
+                         kVgg[last_layer].cout);
+      OIBL_LAUNCH_CHECK();
+    } else {
+      hipLaunchKernelGGL(mx_join_rows_kernel, dim3(blocks), dim3(256), 0, st, (const char*)cur, (float*)feat, n, 0,
+                         1.f / act_scale);
+      OIBL_LAUNCH_CHECK();
+    }
+  }
   if (ev_igemm_end) OIBL_HIP_CHECK(hipEventRecord((hipEvent_t)ev_igemm_end, st));
   return OIBL_OK;
+}
+
+int oibl_vgg16_pool4_forward(const float* x_nchw, int N, int H, int W, const void* const* packed_w_host,
+                             const float* const* bias_host, int precision, float* pool4, void* ws, size_t ws_bytes,
+                             void* stream) {
+  // conv1_1 .. conv4_3 + pool: layers 0 .. 9 of the table
+  return vgg_forward_impl(x_nchw, 0, nullptr, nullptr, N, H, W, packed_w_host, bias_host, precision, pool4, ws,
+                          ws_bytes, stream, nullptr, nullptr, 9);
 }
 
 int oibl_vgg16_conv5_forward_ev(const float* x_nchw, int N, int H, int W,
@@ -3940,7 +3970,7 @@ int oibl_mx_join_rows(const void* src, float* dst, size_t rows, int C, int which
   const size_t n = rows * (size_t)C;
   unsigned b = (unsigned)((n + 255) / 256);
   hipLaunchKernelGGL(mx_join_rows_kernel, dim3(b > 16384 ? 16384 : b), dim3(256), 0, (hipStream_t)stream,
-                     (const char*)src, dst, n, which);
+                     (const char*)src, dst, n, which, 1.f);
   OIBL_LAUNCH_CHECK();
   return OIBL_OK;
 }

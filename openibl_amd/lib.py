@@ -43,6 +43,9 @@ SIGNATURES = {
     "oibl_vgg16_conv5_forward_ev": (c_int, [c_void_p, c_int, c_int, c_int, C.POINTER(c_void_p),
                                             C.POINTER(c_void_p), c_int, c_void_p, c_void_p,
                                             c_size_t, c_void_p, c_void_p, c_void_p]),
+    "oibl_vgg16_pool4_forward": (c_int, [c_void_p, c_int, c_int, c_int, C.POINTER(c_void_p),
+                                         C.POINTER(c_void_p), c_int, c_void_p, c_void_p,
+                                         c_size_t, c_void_p]),
     "oibl_vgg16_u8_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "oibl_vgg16_conv5_forward_u8": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
                                             C.POINTER(c_void_p), C.POINTER(c_void_p), c_int, c_void_p,
@@ -60,6 +63,9 @@ SIGNATURES = {
     "oibl_netvlad_backward_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "oibl_netvlad_backward": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int,
                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "oibl_conv3x3_backward_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
+    "oibl_conv3x3_backward": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p,
+                                      c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "oibl_region_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "oibl_region_vlad_forward": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
                                          c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),

@@ -11,8 +11,10 @@ DDP-saved (`module.`-prefixed) checkpoints load unchanged.  The modules only *ow
     EmbedNet.forward     -> backbone + NetVLAD + norms      (netvlad.py:73-82)
     EmbedNetPCA.forward  -> ... + oibl_pca_forward           (netvlad.py:95-110)
 
-Inference only (the reference's training paths are out of scope; `NetVLAD._init_params`, the
-gradient-free initialisation from k-means centres, is here: oibl_assign_gap).  Inputs must be CUDA(HIP)
+Inference, plus the differentiable part of the reference's default training setting: `EmbedNet.forward_train` carries an
+autograd graph to the NetVLAD layer and, with train_layers='conv5', to conv5_1 .. conv5_3 (oibl_netvlad_backward,
+oibl_conv3x3_backward); the trainers and losses stay in torch (`NetVLAD._init_params`, the gradient-free
+initialisation from k-means centres, is here too: oibl_assign_gap).  Inputs must be CUDA(HIP)
 tensors; there is no CPU path.
 """
 from __future__ import annotations
@@ -278,6 +280,36 @@ class VGG(_PrecisionMixin, nn.Module):
         self.precision_runs["bf16x3(range)"] = self.precision_runs.get("bf16x3(range)", 0) + 1
         return ops.vgg16_conv5(x.contiguous(), ws, bs, "bf16x3")
 
+    def features_train_nhwc(self, x: torch.Tensor) -> torch.Tensor:
+        """The conv5_3 map [N][h][w][512] fp32 with an autograd graph to conv5_1, conv5_2 and conv5_3 (`base[24]`,
+        `base[26]`, `base[28]`: the reference's --layers conv5, ibl/models/vgg.py:20-26, 50-53).  The trunk up to the
+        fourth max-pool is FROZEN: it runs under no_grad in the model's effective precision (ops.vgg16_pool4); an
+        f16mx range flag is read — a host synchronisation — before the graph is built, and a flagged batch (or one
+        beyond the f16mx kernels' 32-bit offsets) is redone in bf16x3.  The three conv5 layers then run in exact fp32
+        on their LIVE parameters (ops.conv3x3_train), whatever the model's precision: their gradients are fp32
+        kernels.  A parameter with requires_grad=False gets no gradient and its stage is not launched."""
+        if x.dtype != torch.float32:
+            x = x.float()
+        x = x.contiguous()
+        prec = self.effective_precision(x)
+        if ops.precision_code(prec) == ops.F16MX and len(self.f16mx_groups(x)) > 1:
+            prec = "bf16x3"
+        with torch.no_grad():
+            ws, bs = self._packed(x.device, prec)
+            self.precision_runs[prec] = self.precision_runs.get(prec, 0) + 1
+            pool4, flag = ops.vgg16_pool4(x, ws, bs, prec, return_flag=True)
+            if flag is not None and int(flag.item()) != 0:
+                self.range_fallbacks += 1
+                self.precision_runs["bf16x3(range)"] = self.precision_runs.get("bf16x3(range)", 0) + 1
+                ws, bs = self._packed(x.device, "bf16x3")
+                pool4 = ops.vgg16_pool4(x, ws, bs, "bf16x3")
+        self._range_flag = None
+        feat = pool4
+        for i in (24, 26, 28):
+            conv = self.base[i]
+            feat = ops.conv3x3_train(feat, conv.weight, conv.bias, relu=i != 28)
+        return feat
+
     def _outputs(self, feat):
         x_nchw = ops.nhwc_to_nchw_f32(feat)
         if self.cut_at_pooling:
@@ -389,7 +421,7 @@ class EmbedNet(_PrecisionMixin, nn.Module):
     def forward(self, x):
         return _with_range_guard(self.base_model, x, self._head)
 
-    def forward_train(self, x):
+    def forward_train(self, x, train_layers=None):
         """(pool_x [N][512], vlad_x [N][K*C]) as `forward`, with vlad_x carrying an autograd graph to
         `net_vlad.conv.weight` and `net_vlad.centroids`: the "train only the VLAD layer" setting, for any loss
         written in torch and any torch optimizer.  The backbone is FROZEN here: it runs under no_grad in the model's
@@ -399,7 +431,25 @@ class EmbedNet(_PrecisionMixin, nn.Module):
         is fp32 (fp32, f16mx, bf16x3); in bf16 the map is widened to fp32 and the fp32 head runs on it, so the bits
         differ from the eval forward's bf16 head.  Unlike the eval forward, which reads the f16mx range flag behind
         the head's launches, this one reads it — a host synchronisation — BEFORE the head is enqueued: the autograd
-        graph must be built on the map that stands."""
+        graph must be built on the map that stands.
+
+        train_layers='conv5' (opt-in; the reference's default --layers conv5): the graph also reaches conv5_1,
+        conv5_2 and conv5_3 — `backward()` fills .grad of their six tensors next to the two of NetVLAD
+        (VGG.features_train_nhwc: frozen trunk up to pool4 in the model's precision, the three layers and their
+        gradients in exact fp32, so vlad_x is the fp32 head on that map, not the eval forward's bits).  The gradient
+        stops at pool4: 'conv4', 'conv3', 'conv2' and 'full' raise NotImplementedError."""
+        if train_layers is not None:
+            if train_layers in ("conv4", "conv3", "conv2", "full"):
+                raise NotImplementedError(f"EmbedNet.forward_train: train_layers={train_layers!r} is not available: "
+                                          "the gradient stops at pool4 (conv5_1 .. conv5_3 and the NetVLAD layer are "
+                                          "trainable on the device; conv4 and below, with the max-pool's backward, "
+                                          "are not)")
+            if train_layers != "conv5":
+                raise ValueError(f"EmbedNet.forward_train: unknown train_layers {train_layers!r}")
+            feat = self.base_model.features_train_nhwc(x)
+            with torch.no_grad():
+                pool_x = ops.global_maxpool_nhwc(feat.detach())
+            return pool_x, self.net_vlad.head_with_grad(feat)
         maps = []
 
         def keep(feat):

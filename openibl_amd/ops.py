@@ -428,6 +428,36 @@ def vgg16_conv5(x: torch.Tensor, weights: Sequence[torch.Tensor], biases: Sequen
     return feat
 
 
+def vgg16_pool4(x: torch.Tensor, weights: Sequence[torch.Tensor], biases: Sequence[torch.Tensor], precision,
+                return_flag: bool = False):
+    """The frozen trunk of conv5 training (oibl_vgg16_pool4_forward): x [N][3][H][W] float32, normalised ->
+    the pooled conv4_3 map [N][H//16][W//16][512], plain fp32 in activation units in every precision; conv1_1 ..
+    conv4_3 + pool run exactly as in `vgg16_conv5` (weights / biases as there; entries 0..9 are read).
+    return_flag: also the pass's f16mx range flag, as `vgg16_conv5` returns it (None in the other precisions)."""
+    p = precision_code(precision)
+    dev = _need_cuda(x, *weights[:10], *biases[:10])
+    if x.dtype != torch.float32 or x.dim() != 4 or x.shape[1] != 3:
+        raise ValueError("vgg16_pool4 expects a float32 [N][3][H][W] tensor")
+    if len(weights) < 10 or len(biases) < 10:
+        raise ValueError("vgg16_pool4 needs the weights and biases of conv1_1 .. conv4_3")
+    N, _, H, W = map(int, x.shape)
+    x = x.contiguous()
+    h, w = vgg16_feature_hw(H, W)
+    lib = _lib.load()
+    ws_bytes = lib.oibl_vgg16_workspace_bytes(N, H, W, p)
+    if ws_bytes == 0:
+        raise ValueError(f"vgg16_pool4: unsupported input shape {tuple(x.shape)}")
+    ws = workspace(ws_bytes, dev, "vgg")
+    out = torch.empty((N, h, w, 512), dtype=torch.float32, device=dev)
+    wp = (C.c_void_p * 13)(*[t.data_ptr() for t in weights[:10]])
+    bp = (C.c_void_p * 13)(*[t.data_ptr() for t in biases[:10]])
+    _lib.check(lib.oibl_vgg16_pool4_forward(_ptr(x), N, H, W, wp, bp, p, _ptr(out), _ptr(ws), ws.numel(),
+                                            _stream(dev)), "vgg16_pool4_forward")
+    if return_flag:
+        return out, (ws[:4].view(torch.int32) if p == F16MX else None)
+    return out
+
+
 def global_maxpool_nhwc(feat: torch.Tensor) -> torch.Tensor:
     """[N][h][w][C] T -> [N][C] fp32 (AdaptiveMaxPool2d(1))."""
     dev = _need_cuda(feat)
@@ -552,6 +582,70 @@ def netvlad_head(feat: torch.Tensor, assign_w: torch.Tensor, centroids: torch.Te
         feat = feat.float()
     _need_cuda(feat, assign_w, centroids)
     return _NetVLADHead.apply(feat, assign_w, centroids, bool(normalize_input))
+
+
+# ---- conv5 training: gradients of a 3x3 convolution -----------------------------------------------
+def conv3x3_backward(x: torch.Tensor, weight: torch.Tensor, grad_out: torch.Tensor,
+                     out_act: Optional[torch.Tensor] = None, want: Sequence[str] = ("w", "b", "x")):
+    """Gradients of conv3x3(pad 1) (+ ReLU) (oibl_conv3x3_backward; nn.Conv2d + nn.ReLU of ibl/models/vgg.py:41-42
+    under autograd).  x [N][H][W][512] fp32 NHWC, the layer's input; weight [512][512][3][3] fp32, the state-dict
+    tensor; grad_out [N][H][W][512] fp32 = dL/d output; out_act: None, or the layer's post-ReLU output — grad_out
+    then counts as 0 where out_act <= 0 -> (grad_weight like weight | None, grad_bias [512] | None, grad_x like x |
+    None) for the letters in `want` ("w", "b", "x").  Exact fp32; bit-identical from run to run; an output does not
+    depend on which others are asked for; an image's grad_x rows do not depend on its batch mates."""
+    dev = _need_cuda(x, weight, grad_out, out_act)
+    want = tuple(want)
+    if not want or any(t not in ("w", "b", "x") for t in want):
+        raise ValueError(f"conv3x3_backward: want must name some of 'w', 'b', 'x' (got {want!r})")
+    if x.dtype != torch.float32 or weight.dtype != torch.float32 or grad_out.dtype != torch.float32 or \
+            (out_act is not None and out_act.dtype != torch.float32):
+        raise ValueError("conv3x3_backward: every tensor must be fp32")
+    if x.dim() != 4 or weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3) or int(weight.shape[1]) != int(x.shape[3]):
+        raise ValueError("conv3x3_backward expects x [N][H][W][Cin] and weight [Cout][Cin][3][3]")
+    N, H, W, cin = map(int, x.shape)
+    cout = int(weight.shape[0])
+    if tuple(grad_out.shape) != (N, H, W, cout) or (out_act is not None and tuple(out_act.shape) != (N, H, W, cout)):
+        raise ValueError(f"conv3x3_backward: grad_out / out_act must be [{N}][{H}][{W}][{cout}]")
+    lib = _lib.load()
+    ws = workspace(lib.oibl_conv3x3_backward_workspace_bytes(N, H, W, cin, cout, int("x" in want)), dev,
+                   "conv_backward")
+    gw = torch.empty(weight.shape, dtype=torch.float32, device=dev) if "w" in want else None
+    gb = torch.empty((cout,), dtype=torch.float32, device=dev) if "b" in want else None
+    gx = torch.empty(x.shape, dtype=torch.float32, device=dev) if "x" in want else None
+    _lib.check(lib.oibl_conv3x3_backward(_ptr(x), N, H, W, cin, _ptr(weight), cout, _ptr(out_act), _ptr(grad_out),
+                                         _ptr(gw), _ptr(gb), _ptr(gx), _ptr(ws), ws.numel(), _stream(dev)),
+               "conv3x3_backward")
+    return gw, gb, gx
+
+
+class _Conv3x3Train(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, bias, relu):
+        w = weight.detach().float().contiguous()
+        y = conv3x3_nhwc(x, pack_conv3x3(w, F32), bias.detach().float().contiguous(), bool(relu), False, F32)
+        ctx.relu = bool(relu)
+        ctx.save_for_backward(x, w, y if relu else None)   # the post-ReLU output is its own mask
+        return y
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        x, w, y = ctx.saved_tensors
+        want = tuple(t for t, n in zip(("x", "w", "b"), ctx.needs_input_grad[:3]) if n)
+        if not want:
+            return None, None, None, None
+        gw, gb, gx = conv3x3_backward(x, w, grad_out.contiguous(), out_act=y, want=want)
+        return gx, gw, gb, None
+
+
+def conv3x3_train(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, relu: bool) -> torch.Tensor:
+    """The differentiable conv3x3(pad 1) + bias (+ ReLU) of conv5 training: x [N][H][W][512] fp32 NHWC, weight
+    [512][512][3][3] and bias [512] the LIVE parameters -> [N][H][W][512] fp32, bit-equal to `pack_conv3x3` +
+    `conv3x3_nhwc` in fp32, with a graph to whichever of x, weight and bias require a gradient; its backward is one
+    call of `conv3x3_backward` for exactly those."""
+    _need_cuda(x, weight, bias)
+    if x.dtype != torch.float32:
+        raise ValueError("conv3x3_train: the activation must be fp32")
+    return _Conv3x3Train.apply(x, weight, bias, bool(relu))
 
 
 # ---- SFRS region similarities ---------------------------------------------------------------------
