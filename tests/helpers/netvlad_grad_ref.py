@@ -21,7 +21,8 @@ EPS = 1e-12
 
 def head_and_grads(x, w, c, G, normalize_input=True):
     """x [N][P][C] (or [N][h][w][C]), w [K][C], c [K][C], G [N][K*C] -> dict of float64 arrays:
-    Y [N][K*C], dW [K][C], dC [K][C], dX shaped like x."""
+    Y [N][K*C], dW [K][C], dC [K][C], dX shaped like x, and the regime of the case: a [N][P][K] the soft-assignment,
+    A [N][K] its column sums, dCn [N][K][C] the images' contributions to dC."""
     shape = np.shape(x)
     x = np.asarray(x, dtype=np.float64).reshape(shape[0], -1, shape[-1])
     w = np.asarray(w, dtype=np.float64)
@@ -33,6 +34,9 @@ def head_and_grads(x, w, c, G, normalize_input=True):
     dW = np.zeros((K, C))
     dC = np.zeros((K, C))
     dX = np.empty_like(x)
+    a_all = np.empty((N, P, K))
+    A_all = np.empty((N, K))
+    dCn = np.empty((N, K, C))
     for n in range(N):
         xn = x[n]
         if normalize_input:
@@ -59,7 +63,8 @@ def head_and_grads(x, w, c, G, normalize_input=True):
             dU = dU - Y[n] * (Y[n] * G[n]).sum() / g
         dV = dU / t
         dV = dV - np.where(tn >= EPS, U * (U * dU).sum(1, keepdims=True) / t, 0.0)
-        dC += -A[:, None] * dV
+        a_all[n], A_all[n], dCn[n] = a, A, -A[:, None] * dV
+        dC += dCn[n]
         da = xh @ dV.T - (dV * c).sum(1)[None, :]
         ds = a * (da - (a * da).sum(1, keepdims=True))
         dW += ds.T @ xh
@@ -68,7 +73,7 @@ def head_and_grads(x, w, c, G, normalize_input=True):
             dX[n] = (dxh - np.where(r_free, xh * (xh * dxh).sum(1, keepdims=True), 0.0)) / r
         else:
             dX[n] = dxh
-    return {"Y": Y.reshape(N, K * C), "dW": dW, "dC": dC, "dX": dX.reshape(shape)}
+    return {"Y": Y.reshape(N, K * C), "dW": dW, "dC": dC, "dX": dX.reshape(shape), "a": a_all, "A": A_all, "dCn": dCn}
 
 
 def rel_l2(got, want) -> float:
@@ -86,3 +91,108 @@ def draw_inputs(seed: int, N: int, h: int, w_: int, K: int = 64, C: int = 512):
     c = rs.rand(K, C).astype(np.float32)
     G = rs.randn(N, K * C).astype(np.float32)
     return x, w, c, G
+
+
+def _trained_params(x, centres, labels, sharpen):
+    """c, w and the regime figures of a trained-like case from its fp32 maps x [M][P][C] (see draw_trained_inputs)."""
+    K, C = centres.shape
+    xd = x.astype(np.float64).reshape(-1, C)
+    d = xd / np.sqrt((xd * xd).sum(1, keepdims=True))              # the normalised descriptors ("traindescs")
+    lab = labels.reshape(-1)
+    c = centres / np.sqrt((centres * centres).sum(1, keepdims=True))
+    for k in range(K):
+        if (lab == k).any():
+            c[k] = d[lab == k].mean(0)
+    c = c.astype(np.float32)                                       # the centroids ("clsts") are these fp32 values
+    cd = c.astype(np.float64)
+    ca = cd / np.sqrt((cd * cd).sum(1, keepdims=True))
+    dots = np.sort(ca @ d.T, axis=0)[::-1]
+    alpha = float(-np.log(0.01) / np.mean(dots[0] - dots[1]))
+    w = (sharpen * (alpha * ca)).astype(np.float32)
+    return w, c, alpha, d
+
+
+def _regime(x, w, c):
+    out = head_and_grads(x, w, c, np.zeros((x.shape[0], w.size)), True)
+    return {"mean_max_a": float(out["a"].max(2).mean()), "min_A": float(out["A"].min())}
+
+
+def draw_trained_inputs(seed: int, N: int, h: int, w_: int, sharpen: float = 1.0, populate: bool = True,
+                        K: int = 64, C: int = 512):
+    """Inputs that look like a conv5_3 map behind its ReLU under the weights NetVLAD._init_params sets
+    (ibl/models/netvlad.py:34-42), for normalize_input=True: (x [N][h][w][C], w [K][C], c [K][C], G [N][K*C], info),
+    the arrays float32.  From one np.random.RandomState(seed), in this order, P = h * w_:
+        centres = randn(K, C)
+        labels[n] = permutation(arange(P) % K) (populate) or randint(0, K, P)           for n = 0 .. N-1
+        noise = randn(N, P, C);  scale = uniform(0.5, 20, (N, P, 1));  G = randn(N, K * C)
+        x = fp32(relu(centres[labels] + 0.5 noise) * scale)          non-negative, about half exact zeros
+    then in float64, from the fp32 x: d_p = x_p / |x_p| over all N P pixels, c_k = fp32(mean of the d_p with label k;
+    centres_k / |centres_k| where no pixel has it), ca_k = c_k / |c_k|, dots = ca d^T sorted descending per pixel,
+        alpha = -ln(0.01) / mean_p(dots[0] - dots[1]),  w = fp32(sharpen * alpha * ca)
+    which is _init_params with clsts = c and traindescs = d, times `sharpen`.  info: alpha, and from the float64
+    forward under (w, c) mean_max_a = mean_{n,p} max_k a_pk and min_A = min_{n,k} A_k; plus `descs` = d."""
+    rs = np.random.RandomState(seed)
+    P = h * w_
+    centres = rs.randn(K, C)
+    labels = np.stack([rs.permutation(np.arange(P) % K) if populate else rs.randint(0, K, P) for _ in range(N)])
+    noise = rs.randn(N, P, C)
+    scale = rs.uniform(0.5, 20.0, (N, P, 1))
+    G = rs.randn(N, K * C).astype(np.float32)
+    x = (np.maximum(centres[labels] + 0.5 * noise, 0.0) * scale).astype(np.float32).reshape(N, h, w_, C)
+    w, c, alpha, d = _trained_params(x, centres, labels, sharpen)
+    info = {"alpha": alpha, **_regime(x, w, c), "descs": d}
+    return x, w, c, G, info
+
+
+def triplet_loss_and_grad(Y, B, n, margin=0.3, eps=1e-6):
+    """The reference's triplet loss (ibl/trainers.py:82-95: F.triplet_margin_loss, p = 2, mean over the B (n - 2)
+    triplets, pairwise_distance's eps added to the difference) of Y [B n][L] in float64, and dL/dY."""
+    Y = np.asarray(Y, dtype=np.float64).reshape(B, n, -1)
+    G = np.zeros_like(Y)
+    loss, T = 0.0, B * (n - 2)
+    for b in range(B):
+        u = Y[b, 0] - Y[b, 1] + eps
+        dap = np.sqrt((u * u).sum())
+        for j in range(2, n):
+            v = Y[b, 0] - Y[b, j] + eps
+            dan = np.sqrt((v * v).sum())
+            li = dap - dan + margin
+            if li > 0:
+                loss += li / T
+                G[b, 0] += (u / dap - v / dan) / T
+                G[b, 1] -= u / dap / T
+                G[b, j] += v / dan / T
+    return loss, G.reshape(B * n, -1)
+
+
+def draw_tuple_inputs(seed: int, B: int, n: int, h: int, w_: int, jitter: float, K: int = 64, C: int = 512):
+    """B tuples of n near-identical trained-like maps under the gradient of the reference's triplet loss: the case
+    in which the images' contributions to dC cancel.  (x [B n][h][w][C], w, c, G [B n][K*C], info), float32.  From
+    one np.random.RandomState(seed), in this order, P = h * w_:
+        centres = randn(K, C);  labels[b] = permutation(arange(P) % K);  noise = randn(B, P, C)
+        scale = uniform(0.5, 20, (B, P, 1));  member = randn(B, n, P, C)
+        x[b, m] = fp32(relu(centres[labels[b]] + 0.5 noise[b] + jitter member[b, m]) * scale[b])
+    w, c as in draw_trained_inputs (sharpen 1) from all B n maps, a member's pixels carrying its tuple's labels.
+    G = fp32(dL/dY), L the triplet loss (margin 0.3) of the float64 Y of this helper; its rows sum to zero within a
+    tuple up to the fp32 rounding (asserted).  info: alpha, mean_max_a, min_A, loss, and cancellation =
+    sum_n |dC_n|_F / |sum_n dC_n|_F in float64."""
+    rs = np.random.RandomState(seed)
+    P = h * w_
+    centres = rs.randn(K, C)
+    labels = np.stack([rs.permutation(np.arange(P) % K) for _ in range(B)])
+    noise = rs.randn(B, P, C)
+    scale = rs.uniform(0.5, 20.0, (B, P, 1))
+    member = rs.randn(B, n, P, C)
+    pre = (centres[labels] + 0.5 * noise)[:, None] + jitter * member
+    x = (np.maximum(pre, 0.0) * scale[:, None]).astype(np.float32).reshape(B * n, h, w_, C)
+    w, c, alpha, _ = _trained_params(x, centres, np.repeat(labels[:, None], n, 1), 1.0)
+    fwd = head_and_grads(x, w, c, np.zeros((B * n, K * C)), True)
+    loss, G64 = triplet_loss_and_grad(fwd["Y"], B, n)
+    G = G64.astype(np.float32)
+    assert loss > 0 and np.abs(G).max() > 0
+    assert np.abs(G.astype(np.float64).reshape(B, n, -1).sum(1)).max() <= 1e-6 * np.abs(G).max()
+    out = head_and_grads(x, w, c, G, True)
+    cancellation = float(np.sqrt((out["dCn"] ** 2).sum((1, 2))).sum() / np.sqrt((out["dC"] ** 2).sum()))
+    info = {"alpha": alpha, "mean_max_a": float(out["a"].max(2).mean()), "min_A": float(out["A"].min()),
+            "loss": float(loss), "cancellation": cancellation}
+    return x, w, c, G, info

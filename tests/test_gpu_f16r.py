@@ -124,7 +124,8 @@ def test_near_duplicate_gallery_overflows_into_the_exact_path(dev):
     # the repeat takes the K2 nearest of the fp32 tiles and rescores them: query 0's list is ten of the 200 rows that
     # sit 1e-12 from it (any ten: they are fp64 near-ties), every other query's list is the fp32 mode's
     assert torch.equal(i[1:], i32[1:])
-    assert bool(((i[0] >= 1000) & (i[0] < 1200)).all()) and float(v[0].abs().max()) < 1e-6
+    # (row 0, which the 200 were drawn around, is as near as they are and may be one of the ten)
+    assert bool((((i[0] >= 1000) & (i[0] < 1200)) | (i[0] == 0)).all()) and float(v[0].abs().max()) < 1e-6
     _assert_lists("f16r after overflow", q, g, v, i, k)
     ve, ie = ops.sqdist_topk(q.to(dev), g.to(dev), k, precision="f16r", exact=True)
     assert torch.equal(ie, i) and torch.equal(ve, v)

@@ -17,6 +17,25 @@ ENTRIES = ("oibl_netvlad_backward_workspace_bytes", "oibl_netvlad_backward")
 CONTRACTIONS = ("nvb_contract_kernel", "nvb_aggregate_kernel", "nvb_dx_kernel")
 STREAMING = ("nvb_assign_kernel", "nvb_rowstats_kernel", "nvb_dv_kernel", "nvb_reduce_kernel")
 CASES = ("netvlad_backward_2x3x5_norm", "netvlad_backward_3x4x6_raw")
+TRAINED = "netvlad_backward_trained_2x12x16"
+SATURATED = "netvlad_backward_saturated_2x8x8"
+TUPLE = "netvlad_backward_tuple_1x4x8x8"
+_drawn = {}
+
+
+def draw_regime_case(name):
+    """(inputs, info, float64 gradients) of one of the three trained-regime fixtures, from its seed; once per session."""
+    if name not in _drawn:
+        z = np.load(GOLDEN / f"{name}.npz")
+        N, h, w_, C = map(int, z["shape"])
+        if name == TUPLE:
+            B, n = map(int, z["tuple"])
+            assert B * n == N
+            x, w, c, G, info = ref.draw_tuple_inputs(int(z["seed"]), B, n, h, w_, float(z["jitter"]))
+        else:
+            x, w, c, G, info = ref.draw_trained_inputs(int(z["seed"]), N, h, w_, sharpen=float(z["sharpen"]))
+        _drawn[name] = ((x, w, c, G), info, ref.head_and_grads(x, w, c, G, True))
+    return _drawn[name]
 
 
 @pytest.mark.parametrize("name", CASES)
@@ -36,6 +55,75 @@ def test_float64_helper_against_the_reference_autograd(name):
     assert max(errs.values()) <= 1e-5, errs
     np.testing.assert_allclose([errs["dW"], errs["dC"], errs["dX"]], z["ref_err"], rtol=1e-6)
     assert (GOLDEN / f"{name}.npz").stat().st_size < 500_000
+
+
+@pytest.mark.parametrize("name", (TRAINED, SATURATED, TUPLE))
+def test_float64_helper_against_the_reference_autograd_in_the_trained_regime(name):
+    """As above for the three fixtures of the regime a training run is in.  dX is stored at every dx_stride-th pixel
+    of an image: `ref_err` is the generator's figure over the full arrays (dW, dC reproduce it), `ref_err_dx_stored`
+    the one over the stored rows.  dW of the saturated case tends to zero with the softmax's saturation; the generator
+    does not assert its error, and neither does this test beyond reproducing the stored figure."""
+    z = np.load(GOLDEN / f"{name}.npz")
+    N, h, w_, C = map(int, z["shape"])
+    (x, w, c, G), info, want = draw_regime_case(name)
+    assert x.shape == (N, h, w_, C) and bool(z["normalize_input"])
+    stride, dxs = int(z["vlad_stride"]), int(z["dx_stride"])
+    errs = {"Y": ref.rel_l2(z["vlad_x"], want["Y"][:, ::stride]),
+            "dW": ref.rel_l2(z["dW"], want["dW"]), "dC": ref.rel_l2(z["dC"], want["dC"]),
+            "dX": ref.rel_l2(z["dX"], want["dX"].reshape(N, h * w_, C)[:, ::dxs])}
+    print(name, errs, "stored", z["ref_err"].tolist(), float(z["ref_err_dx_stored"]))
+    assert z["dW"].shape == want["dW"].shape and z["dC"].shape == want["dC"].shape
+    judged = {k: v for k, v in errs.items() if not (name == SATURATED and k == "dW")}
+    assert max(judged.values()) <= 1e-5, errs
+    assert float(z["ref_err"][1]) <= 1e-5 and float(z["ref_err"][2]) <= 1e-5
+    np.testing.assert_allclose([errs["dW"], errs["dC"]], z["ref_err"][:2], rtol=1e-6)
+    np.testing.assert_allclose(errs["dX"], float(z["ref_err_dx_stored"]), rtol=1e-6)
+    for k in ("alpha", "mean_max_a", "min_A"):
+        np.testing.assert_allclose(info[k], float(z[k]), rtol=1e-9)
+    if name == TUPLE:
+        np.testing.assert_allclose(info["cancellation"], float(z["cancellation"]), rtol=1e-6)
+    assert (GOLDEN / f"{name}.npz").stat().st_size < 500_000
+
+
+@pytest.mark.parametrize("name", (TRAINED, SATURATED, TUPLE, "random labels"))
+def test_trained_recipes_are_deterministic(name):
+    """Two draws from the seed are the same bits: the fixtures' inputs, and a draw with random labels."""
+    if name == "random labels":
+        a, b = ref.draw_trained_inputs(54, 3, 5, 8, 4.0, False), ref.draw_trained_inputs(54, 3, 5, 8, 4.0, False)
+    else:
+        inputs, info, _ = draw_regime_case(name)
+        a = inputs + (info,)
+        _drawn.pop(name)
+        inputs, info, _ = draw_regime_case(name)
+        b = inputs + (info,)
+    for s, t in zip(a[:4], b[:4]):
+        assert s is not t and s.dtype == np.float32 and s.tobytes() == t.tobytes()
+    assert {k: v for k, v in a[4].items() if k != "descs"} == {k: v for k, v in b[4].items() if k != "descs"}
+
+
+def test_regimes_of_the_cases():
+    """What the fixtures are for, on the helper's float64 values: the trained and the tuple case have a peaked but
+    unsaturated soft-assignment, the saturated one is saturated, the populated ones leave no cluster empty (with
+    a saturated softmax AND near-empty clusters fp32 autograd itself is wrong by half: that regime is no yardstick),
+    the tuple's dC contributions cancel at least 10-fold — and draw_inputs under normalize_input is the uniform
+    regime: a_pk is 1/64 within some 10 %."""
+    for name in (TRAINED, TUPLE):
+        info = draw_regime_case(name)[1]
+        print(name, {k: v for k, v in info.items() if k != "descs"})
+        assert 0.6 <= info["mean_max_a"] <= 0.9
+    assert draw_regime_case(SATURATED)[1]["mean_max_a"] >= 0.999
+    for name in (TRAINED, SATURATED):
+        assert draw_regime_case(name)[1]["min_A"] >= 0.5
+    assert draw_regime_case(TUPLE)[1]["cancellation"] >= 10.0
+    x, w, c, G = ref.draw_inputs(41, 2, 3, 5)
+    a = ref.head_and_grads(x, w, c, G, True)["a"]
+    print("draw_inputs, normalised: mean max_k a_pk", a.max(2).mean())
+    assert a.max(2).mean() <= 0.05
+    # about half of a trained-like map is exact zeros, none of it is negative, and the tuple's G rows cancel
+    (x, _, _, _), _, _ = draw_regime_case(TRAINED)
+    assert x.min() == 0.0 and 0.4 <= (x == 0).mean() <= 0.6
+    G = draw_regime_case(TUPLE)[0][3]
+    assert np.abs(G.astype(np.float64).sum(0)).max() <= 1e-6 * np.abs(G).max()
 
 
 def test_header_declares_and_library_exports_the_backward_entries():
