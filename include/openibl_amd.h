@@ -338,6 +338,41 @@ int oibl_netvlad_backward(const void* feat, int N, int P, int K, int C, int prec
                           const float* grad_vlad_norm, float* grad_assign_w, float* grad_centroids,
                           float* grad_feat, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- SFRS region head: gradients ---------------------------------------------------- *
+ * The backward of oibl_region_vlad_forward and oibl_region_scores, i.e. of EmbedRegionNet._compute_region_sim
+ * (ibl/models/netvlad.py:123-186) as torch autograd differentiates it under SFRSTrainer._forward
+ * (ibl/trainers.py:235-259).  Stateless like oibl_netvlad_backward: per-pixel norms, soft-assignment and the four
+ * quarter aggregates are recomputed from `feat`; the reference's residual[N*4][K][C][P/4] never exists.
+ * oibl_region_vlad_backward: feat [N][h][w][C] fp32 (precision must be OIBL_F32; h and w even and >= 2, K = 64,
+ *   C = 512, N <= 65535), grad_region_vlad [N][9][K*C] fp32 = dL/d region_vlad, regions in the forward's order.
+ *   Outputs, each optional (may be NULL, at least one is needed), OVERWRITTEN, not accumulated into; a stage whose
+ *   output is NULL is not launched:
+ *     grad_assign_w  [K][C]        summed over the images in image order
+ *     grad_centroids [K][C]        summed over the images in image order
+ *     grad_feat      [N][h][w][C]  dL/d feat
+ *   The heavy contractions are exact fp32 (v_mfma_f32_32x32x2_f32); logits, norms, the normalisations' backward and
+ *   the per-image grad_centroids are fp64 (a tuple loss's contributions to grad_centroids cancel over a tuple).
+ *   No floating-point atomics: bit-identical from run to run, an output does not depend on which other outputs are
+ *   requested, an image's grad_feat rows do not depend on its batch mates.  Measured against float64 (rel-L2, maps
+ *   of 2 x 2 to 30 x 40): dW 3.3e-7 .. 1.8e-6, dC 3.6e-8 .. 9.5e-7, dX 2.5e-7 .. 1.2e-6
+ *   (tests/test_gpu_region_backward.py).
+ *   Workspace from oibl_region_backward_workspace_bytes (linear in N, smaller without grad_feat; 0 for an invalid
+ *   shape), 256-byte aligned; the other pointers 16-byte aligned.
+ * oibl_region_scores_backward: region_vlad [T*per_tuple][9][L] as given to oibl_region_scores, grad_score
+ *   [T][per_tuple-1][9][9] -> grad_region_vlad [T*per_tuple][9][L], OVERWRITTEN:
+ *     anchor  dY[t,0][a]   = sum_j sum_b grad_score[t][j][a][b] Y[t,1+j][b]   (pairs in order, fp64 accumulators)
+ *     pair j  dY[t,1+j][b] = sum_a grad_score[t][j][a][b] Y[t,0][a]
+ *   A pair's rows do not depend on the other pairs.
+ * Invalid arguments (a null input, no output, odd h or w, K != 64, C != 512, another precision, per_tuple < 2) return
+ * OIBL_E_INVALID, a short or misaligned workspace OIBL_E_WORKSPACE; nothing is launched then.                     */
+size_t oibl_region_backward_workspace_bytes(int N, int h, int w, int K, int C, int want_grad_feat);
+int oibl_region_vlad_backward(const void* feat, int N, int h, int w, int K, int C, int precision,
+                              const float* assign_w, const float* centroids, int normalize_input,
+                              const float* grad_region_vlad, float* grad_assign_w, float* grad_centroids,
+                              float* grad_feat, void* ws, size_t ws_bytes, void* stream);
+int oibl_region_scores_backward(const float* region_vlad, int T, int per_tuple, int L, const float* grad_score,
+                                float* grad_region_vlad, void* stream);
+
 /* ---- 3x3 convolution (+ ReLU): gradients -------------------------------------------- *
  * The backward of nn.Conv2d(Cin, Cout, 3, padding=1) followed by nn.ReLU (ibl/models/vgg.py:41-42, 61-62) as torch
  * autograd differentiates them: what trains conv5_1 .. conv5_3, the layers the reference's scripts leave unfrozen

@@ -70,6 +70,11 @@ SIGNATURES = {
     "oibl_region_vlad_forward": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
                                          c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "oibl_region_scores": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "oibl_region_backward_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
+    "oibl_region_vlad_backward": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                                          c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                          c_void_p]),
+    "oibl_region_scores_backward": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "oibl_rerank_row_extremes_workspace_bytes": (c_size_t, [c_int, c_int]),
     "oibl_rerank_row_extremes": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "oibl_rerank_set_stride": (c_int, [c_int, c_int]),

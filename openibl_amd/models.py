@@ -524,10 +524,13 @@ def GraphedDescriptor(model: "EmbedNetPCA", example: torch.Tensor, pipeline: boo
 
 class EmbedRegionNet(_PrecisionMixin, nn.Module):
     """ibl/models/netvlad.py:112-207.  forward() is the evaluation branch (:199-205, identical to
-    EmbedNet.forward).  The SFRS region-similarity branch (:123-194) is forward-only here — the reference runs it
-    on the frozen previous-generation model under torch.no_grad() (ibl/trainers.py:243-244) — and is reached
-    through `region_similarity(x)`; forward() in training mode keeps raising: this package has no autograd, and
-    gradient-free tensors handed to a trainer would be a trap."""
+    EmbedNet.forward).  The SFRS region-similarity branch (:123-194) is reached through two methods:
+    `region_similarity(x)`, without gradients — what the reference runs on the frozen previous-generation model
+    under torch.no_grad() (ibl/trainers.py:243-244) — and `forward_train(x, train_layers)`, the same three outputs
+    with an autograd graph to the NetVLAD layer (and conv5), whose backward runs on the device (ops.region_vlad_train,
+    ops.region_scores_train): the student's two calls in SFRSTrainer._forward (:240, :245).  forward() in training
+    mode keeps raising: it is no_grad like every forward() of this package, and gradient-free tensors handed to a
+    trainer would be a trap."""
 
     def __init__(self, base_model, net_vlad, tuple_size=1):
         super().__init__()
@@ -588,6 +591,54 @@ class EmbedRegionNet(_PrecisionMixin, nn.Module):
             raise ValueError(f"EmbedRegionNet.region_similarity: the conv5 map of a {H} x {W} image is {h} x {w}, "
                              f"both sides must be even to cut it into quarters")
         return _with_range_guard(self.base_model, x, self._region_head)
+
+    def _region_head_train(self, feat):
+        """_region_head with a graph: the live parameters, the differentiable head and scores."""
+        T, per = self._tuple_shape(int(feat.shape[0]))
+        nv = self.net_vlad
+        vec = ops.region_vlad_train(feat, nv.conv.weight, nv.centroids, nv.normalize_input)
+        score = ops.region_scores_train(vec, T)
+        vec = vec.view(T, per, 9, vec.shape[-1])
+        return score, vec[:, :1], vec[:, 1:]
+
+    def forward_train(self, x, train_layers=None):
+        """(score [T][n][9][9], vlad_A [T][1][9][L], vlad_B [T][n][9][L]) as `region_similarity`, carrying an autograd
+        graph to `net_vlad.conv.weight` and `net_vlad.centroids`: the reference's training-mode forward
+        (_forward_train, netvlad.py:188-194) for any loss written in torch.  All three outputs are differentiable —
+        SFRSTrainer._forward reads vlad_A / vlad_B for loss_hard and score for loss_soft — and autograd adds the two
+        gradients that reach the region vectors.  The backbone is FROZEN here: it runs under no_grad in the model's
+        precision through the range guard, and the f16mx range flag is read — a host synchronisation — BEFORE the head
+        is enqueued, as in EmbedNet.forward_train.  The values are bit-equal to `region_similarity(x)` where the conv5
+        map is fp32 (fp32, f16mx, bf16x3); a bf16 map is widened to fp32 in both.
+
+        train_layers='conv5': the map comes from `base_model.features_train_nhwc(x)` and the graph also reaches the
+        six conv5 tensors.  'conv4', 'conv3', 'conv2' and 'full' raise NotImplementedError: the gradient stops at
+        pool4."""
+        if x.dim() != 4:
+            raise ValueError("EmbedRegionNet.forward_train: images [N][3][H][W]")
+        self._tuple_shape(int(x.shape[0]))
+        H, W = (int(x.shape[1]), int(x.shape[2])) if x.dtype == torch.uint8 else (int(x.shape[2]), int(x.shape[3]))
+        h, w = ops.vgg16_feature_hw(H, W)
+        if h % 2 or w % 2:
+            raise ValueError(f"EmbedRegionNet.forward_train: the conv5 map of a {H} x {W} image is {h} x {w}, "
+                             f"both sides must be even to cut it into quarters")
+        if train_layers is not None:
+            if train_layers in ("conv4", "conv3", "conv2", "full"):
+                raise NotImplementedError(f"EmbedRegionNet.forward_train: train_layers={train_layers!r} is not "
+                                          "available: the gradient stops at pool4 (conv5_1 .. conv5_3 and the NetVLAD "
+                                          "layer are trainable on the device; conv4 and below are not)")
+            if train_layers != "conv5":
+                raise ValueError(f"EmbedRegionNet.forward_train: unknown train_layers {train_layers!r}")
+            return self._region_head_train(self.base_model.features_train_nhwc(x))
+        maps = []
+
+        def keep(feat):
+            maps.append(feat)
+            return None
+
+        with torch.no_grad():
+            _with_range_guard(self.base_model, x, keep)
+        return self._region_head_train(maps[-1])
 
     @torch.no_grad()
     def _compute_region_sim(self, feature_A, feature_B):

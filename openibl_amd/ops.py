@@ -695,6 +695,120 @@ def region_scores(region_vlad: torch.Tensor, tuple_size: int) -> torch.Tensor:
     return score
 
 
+def region_vlad_backward(feat: torch.Tensor, assign_w: torch.Tensor, centroids: torch.Tensor, grad_out: torch.Tensor,
+                         normalize_input: bool = True, want: Sequence[str] = ("w", "c", "x")):
+    """Gradients of `region_vlad(...)` (oibl_region_vlad_backward).  feat [N][h][w][C] fp32, h and w even, grad_out
+    [N][9][K*C] fp32 = dL/d region_vlad -> (grad_assign_w [K][C] | None, grad_centroids [K][C] | None, grad_feat like
+    feat | None) for the letters in `want` ("w", "c", "x").  Stateless: the forward's intermediates are recomputed
+    from feat.  Bit-identical from run to run; an output does not depend on which others are asked for."""
+    dev = _need_cuda(feat, assign_w, centroids, grad_out)
+    want = tuple(want)
+    if not want or any(t not in ("w", "c", "x") for t in want):
+        raise ValueError(f"region_vlad_backward: want must name some of 'w', 'c', 'x' (got {want!r})")
+    if feat.dim() != 4 or feat.dtype != torch.float32 or grad_out.dtype != torch.float32:
+        raise ValueError("region_vlad_backward: feature map [N][h][w][C] and grad_out must be fp32")
+    if not feat.is_contiguous() or not grad_out.is_contiguous():
+        raise ValueError("region_vlad_backward: feature map and grad_out must be contiguous")
+    N, h, w, C_ = map(int, feat.shape)
+    if h % 2 or w % 2 or h == 0 or w == 0:
+        raise ValueError(f"region_vlad_backward: the conv5 map is {h} x {w}, both sides must be even to cut it into "
+                         f"quarters")
+    K = int(centroids.shape[0])
+    aw = assign_w.reshape(K, C_)
+    if aw.dtype != torch.float32 or centroids.dtype != torch.float32 or not aw.is_contiguous() \
+            or not centroids.is_contiguous():
+        raise ValueError("region_vlad_backward: assign_w / centroids must be contiguous float32")
+    if grad_out.numel() != N * 9 * K * C_:
+        raise ValueError(f"region_vlad_backward: grad_out has {grad_out.numel()} elements, expected {N} x 9 x {K * C_}")
+    lib = _lib.load()
+    ws = workspace(lib.oibl_region_backward_workspace_bytes(N, h, w, K, C_, int("x" in want)), dev, "region_backward")
+    gw = torch.empty((K, C_), dtype=torch.float32, device=dev) if "w" in want else None
+    gc = torch.empty((K, C_), dtype=torch.float32, device=dev) if "c" in want else None
+    gx = torch.empty(feat.shape, dtype=torch.float32, device=dev) if "x" in want else None
+    _lib.check(lib.oibl_region_vlad_backward(_ptr(feat), N, h, w, K, C_, F32, _ptr(aw), _ptr(centroids),
+                                             int(normalize_input), _ptr(grad_out), _ptr(gw), _ptr(gc), _ptr(gx),
+                                             _ptr(ws), ws.numel(), _stream(dev)), "region_vlad_backward")
+    return gw, gc, gx
+
+
+def region_scores_backward(region_vlad: torch.Tensor, grad_score: torch.Tensor, tuple_size: int) -> torch.Tensor:
+    """Gradient of `region_scores(region_vlad, tuple_size)` (oibl_region_scores_backward): region_vlad
+    [T*(1+n)][9][L] fp32 as given to the forward, grad_score [T][n][9][9] fp32 -> dL/d region_vlad, same shape."""
+    dev = _need_cuda(region_vlad, grad_score)
+    if region_vlad.dim() != 3 or int(region_vlad.shape[1]) != 9 or region_vlad.dtype != torch.float32 \
+            or not region_vlad.is_contiguous():
+        raise ValueError("region_scores_backward: region_vlad must be a contiguous float32 [N][9][L] tensor")
+    N, _, L = map(int, region_vlad.shape)
+    T = int(tuple_size)
+    if T <= 0 or N % T:
+        raise ValueError(f"region_scores_backward: {N} images are not a multiple of tuple_size {T}")
+    if N // T < 2:
+        raise ValueError(f"region_scores_backward: a tuple needs an anchor and at least one pair (got {N // T} image "
+                         f"per tuple)")
+    if grad_score.dtype != torch.float32 or not grad_score.is_contiguous() \
+            or tuple(grad_score.shape) != (T, N // T - 1, 9, 9):
+        raise ValueError(f"region_scores_backward: grad_score must be a contiguous float32 [{T}][{N // T - 1}][9][9]")
+    out = torch.empty_like(region_vlad)
+    _lib.check(_lib.load().oibl_region_scores_backward(_ptr(region_vlad), T, N // T, L, _ptr(grad_score), _ptr(out),
+                                                       _stream(dev)), "region_scores_backward")
+    return out
+
+
+class _RegionVLAD(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, feat, assign_w, centroids, normalize_input):
+        ctx.save_for_backward(feat, assign_w, centroids)
+        ctx.normalize_input = bool(normalize_input)
+        return region_vlad(feat, assign_w, centroids, normalize_input=ctx.normalize_input)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        feat, assign_w, centroids = ctx.saved_tensors
+        want = tuple(t for t, n in zip(("x", "w", "c"), ctx.needs_input_grad[:3]) if n)
+        if not want:
+            return None, None, None, None
+        gw, gc, gx = region_vlad_backward(feat, assign_w, centroids, grad_out.contiguous(),
+                                          normalize_input=ctx.normalize_input, want=want)
+        if gw is not None:
+            gw = gw.reshape(assign_w.shape)
+        return gx, gw, gc, None
+
+
+class _RegionScores(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, vec, tuple_size):
+        ctx.save_for_backward(vec)
+        ctx.tuple_size = int(tuple_size)
+        return region_scores(vec, ctx.tuple_size)
+
+    @staticmethod
+    def backward(ctx, grad_score):
+        (vec,) = ctx.saved_tensors
+        if not ctx.needs_input_grad[0]:
+            return None, None
+        return region_scores_backward(vec, grad_score.contiguous(), ctx.tuple_size), None
+
+
+def region_vlad_train(feat: torch.Tensor, assign_w: torch.Tensor, centroids: torch.Tensor,
+                      normalize_input: bool = True) -> torch.Tensor:
+    """The differentiable region head: [N][9][K*C], bit-equal to `region_vlad`, with a graph to whichever of feat,
+    assign_w ([K][C] or conv.weight's [K][C][1][1]) and centroids require a gradient; its backward is one call of
+    `region_vlad_backward` for exactly those.  A bf16 map is widened to fp32 first, as `netvlad_head` does."""
+    if feat.dtype == torch.bfloat16:
+        feat = feat.float()
+    _need_cuda(feat, assign_w, centroids)
+    if feat.dtype != torch.float32:
+        raise ValueError("region_vlad_train: feature map must be bf16 or fp32")
+    return _RegionVLAD.apply(feat.contiguous(), assign_w, centroids, bool(normalize_input))
+
+
+def region_scores_train(vec: torch.Tensor, tuple_size: int) -> torch.Tensor:
+    """The differentiable `region_scores`: score [T][n][9][9], bit-equal to it, its backward one call of
+    `region_scores_backward`.  Autograd adds this gradient to the one that reaches `vec` from its direct use."""
+    _need_cuda(vec)
+    return _RegionScores.apply(vec, int(tuple_size))
+
+
 # ---- PCA --------------------------------------------------------------------------------------
 class PcaWeight:
     """A PCA weight [d][D] resident on the device, with — fp32 only — the re-packed copy the streaming kernel
