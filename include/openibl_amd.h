@@ -373,6 +373,59 @@ int oibl_region_vlad_backward(const void* feat, int N, int h, int w, int K, int 
 int oibl_region_scores_backward(const float* region_vlad, int T, int per_tuple, int L, const float* grad_score,
                                 float* grad_region_vlad, void* stream);
 
+/* ---- Tuple losses and the soft-label loss, forward and backward --------------------- *
+ * The losses of Trainer._get_loss (ibl/trainers.py:82-162), SFRSTrainer._get_loss / _get_hard_loss (:261-320) and
+ * the soft term of SFRSTrainer._forward (:256-257), each fused into at most two launches forward and one backward.
+ * A tuple is an anchor, a positive and M negatives, rows of L fp32 with a contiguous last dimension:
+ *   anchors [B] rows stride_a apart, positives [B] rows stride_p apart, negatives [B][M] rows at
+ *   b * stride_n_tuple + j * stride_n_row — strides in ELEMENTS, >= 0, so strided views (region 0 of a
+ *   [B][1+M][9][L] tensor: row stride 9 L) are read in place.  Rows are read with 16-byte loads where the three base
+ *   pointers are 16-byte aligned and every stride is a multiple of 4, with 4-byte loads otherwise: same bits.
+ *   mode   OIBL_LOSS_TRIPLET     F.triplet_margin_loss(margin, p=2, reduction='mean') over the B M triples, with
+ *                                pairwise_distance's eps = 1e-6 added to the difference; `score` and `temp` unused
+ *          OIBL_LOSS_SARE_JOINT  mean over B of -log_softmax([z_pos, z_neg_1 .. z_neg_M])[0]
+ *          OIBL_LOSS_SARE_IND    mean over B M of -log_softmax([z_pos, z_neg_j])[0]
+ *   score  OIBL_SCORE_SQDIST     z = -|a - x|^2 (Trainer; `temp` unused)
+ *          OIBL_SCORE_DOT        z = <a, x> / temp (SFRSTrainer), temp > 0
+ * oibl_tuple_loss_forward -> loss (one fp32) and coef [B][1+M] fp64: per row of a tuple (positive first) the factor
+ *   its gradient is a multiple of, 1 / count included.  Distances and dots, the hinge, the softmax and the table are
+ *   fp64; a row is reduced in 8 chunks summed in chunk order.
+ * oibl_tuple_loss_backward: the same rows, the table and grad_loss, a DEVICE pointer to the upstream fp32 scalar (no
+ *   host synchronisation) -> compact grad_anchors [B][L], grad_positives [B][L], grad_negatives [B][M][L] fp32,
+ *   OVERWRITTEN; each may be NULL (at least one is needed) and is then not computed.  A triplet whose hinge is
+ *   inactive contributes exactly zero.
+ * No atomics: bit-identical from run to run; a tuple's gradients depend on its batch mates through 1 / count only.
+ * Limits: 1 <= B <= 65535, 1 <= M <= OIBL_TUPLE_LOSS_MAX_NEG, L >= 1.
+ * Soft-label loss: student, teacher [B][J] fp32 contiguous ->
+ *   loss = (-softmax(teacher / temp_teacher) * log_softmax(student / temp_student)).mean(0).sum(), one workgroup per
+ *   row in fp64, and coef [B][J] fp64 = (softmax(student / temp_student) - softmax(teacher / temp_teacher)) /
+ *   (B temp_student); the backward writes grad_student [B][J] = coef x *grad_loss.  1 <= B <= 65535,
+ *   1 <= J <= OIBL_SOFT_LABEL_MAX_J, both temperatures > 0.
+ * Workspaces from the two queries (0 outside the limits), 256-byte aligned; the tables 8-byte aligned.  Invalid
+ * arguments return OIBL_E_INVALID, a short or misaligned workspace OIBL_E_WORKSPACE; nothing is launched then.    */
+#define OIBL_LOSS_TRIPLET 0
+#define OIBL_LOSS_SARE_JOINT 1
+#define OIBL_LOSS_SARE_IND 2
+#define OIBL_SCORE_SQDIST 0
+#define OIBL_SCORE_DOT 1
+#define OIBL_TUPLE_LOSS_MAX_NEG 64
+#define OIBL_SOFT_LABEL_MAX_J 4096
+size_t oibl_tuple_loss_workspace_bytes(int B, int M);
+int oibl_tuple_loss_forward(const float* anchors, long long stride_a, const float* positives, long long stride_p,
+                            const float* negatives, long long stride_n_tuple, long long stride_n_row, int B, int M,
+                            int L, int mode, int score, double margin, double temp, float* loss, double* coef,
+                            void* ws, size_t ws_bytes, void* stream);
+int oibl_tuple_loss_backward(const float* anchors, long long stride_a, const float* positives, long long stride_p,
+                             const float* negatives, long long stride_n_tuple, long long stride_n_row, int B, int M,
+                             int L, int mode, int score, const double* coef, const float* grad_loss,
+                             float* grad_anchors, float* grad_positives, float* grad_negatives, void* stream);
+size_t oibl_soft_label_loss_workspace_bytes(int B, int J);
+int oibl_soft_label_loss_forward(const float* student, const float* teacher, int B, int J, double temp_student,
+                                 double temp_teacher, float* loss, double* coef, void* ws, size_t ws_bytes,
+                                 void* stream);
+int oibl_soft_label_loss_backward(const double* coef, int B, int J, const float* grad_loss, float* grad_student,
+                                  void* stream);
+
 /* ---- 3x3 convolution (+ ReLU): gradients -------------------------------------------- *
  * The backward of nn.Conv2d(Cin, Cout, 3, padding=1) followed by nn.ReLU (ibl/models/vgg.py:41-42, 61-62) as torch
  * autograd differentiates them: what trains conv5_1 .. conv5_3, the layers the reference's scripts leave unfrozen

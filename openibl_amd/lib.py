@@ -75,6 +75,17 @@ SIGNATURES = {
                                           c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
                                           c_void_p]),
     "oibl_region_scores_backward": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "oibl_tuple_loss_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "oibl_tuple_loss_forward": (c_int, [c_void_p, C.c_longlong, c_void_p, C.c_longlong, c_void_p, C.c_longlong,
+                                        C.c_longlong, c_int, c_int, c_int, c_int, c_int, C.c_double, C.c_double,
+                                        c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "oibl_tuple_loss_backward": (c_int, [c_void_p, C.c_longlong, c_void_p, C.c_longlong, c_void_p, C.c_longlong,
+                                         C.c_longlong, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                                         c_void_p, c_void_p, c_void_p, c_void_p]),
+    "oibl_soft_label_loss_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "oibl_soft_label_loss_forward": (c_int, [c_void_p, c_void_p, c_int, c_int, C.c_double, C.c_double, c_void_p,
+                                             c_void_p, c_void_p, c_size_t, c_void_p]),
+    "oibl_soft_label_loss_backward": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "oibl_rerank_row_extremes_workspace_bytes": (c_size_t, [c_int, c_int]),
     "oibl_rerank_row_extremes": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "oibl_rerank_set_stride": (c_int, [c_int, c_int]),

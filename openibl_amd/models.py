@@ -13,7 +13,7 @@ DDP-saved (`module.`-prefixed) checkpoints load unchanged.  The modules only *ow
 
 Inference, plus the differentiable part of the reference's default training setting: `EmbedNet.forward_train` carries an
 autograd graph to the NetVLAD layer and, with train_layers='conv5', to conv5_1 .. conv5_3 (oibl_netvlad_backward,
-oibl_conv3x3_backward); the trainers and losses stay in torch (`NetVLAD._init_params`, the gradient-free
+oibl_conv3x3_backward); the training loops and their fused losses are ibl.trainers (`NetVLAD._init_params`, the gradient-free
 initialisation from k-means centres, is here too: oibl_assign_gap).  Inputs must be CUDA(HIP)
 tensors; there is no CPU path.
 """

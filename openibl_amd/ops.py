@@ -809,6 +809,172 @@ def region_scores_train(vec: torch.Tensor, tuple_size: int) -> torch.Tensor:
     return _RegionScores.apply(vec, int(tuple_size))
 
 
+# ---- training losses ----------------------------------------------------------------------------
+LOSS_KINDS = {"triplet": 0, "sare_joint": 1, "sare_ind": 2}
+LOSS_SCORES = {"sqdist": 0, "dot": 1}
+TUPLE_LOSS_MAX_NEG = 64
+SOFT_LABEL_MAX_J = 4096
+
+
+def _tuple_rows(what: str, anchors: torch.Tensor, positives: torch.Tensor, negatives: torch.Tensor):
+    """Validate the three inputs of a tuple loss (strided views welcome: only the last dimension must be contiguous)
+    and return (device, B, M, L)."""
+    shapes = f"anchors {tuple(anchors.shape)}, positives {tuple(positives.shape)}, negatives {tuple(negatives.shape)}"
+    for t in (anchors, positives, negatives):
+        if not t.is_cuda:
+            raise _lib.OpenIBLAmdError(f"openibl_amd: {what}: tensor is on {t.device}; this path runs only on an AMD "
+                                       "GPU through the HIP extension (there is no CPU fallback)")
+        if t.device != anchors.device:
+            raise ValueError(f"{what}: tensors on different devices")
+        if t.dtype != torch.float32:
+            raise ValueError(f"{what}: float32 tensors only (got {t.dtype}; {shapes})")
+    if anchors.dim() != 2 or positives.shape != anchors.shape or negatives.dim() != 3 \
+            or negatives.shape[0] != anchors.shape[0] or negatives.shape[2] != anchors.shape[1]:
+        raise ValueError(f"{what}: anchors [B][L], positives [B][L] and negatives [B][M][L] are expected (got {shapes})")
+    B, M, L = map(int, negatives.shape)
+    if B < 1 or L < 1 or not 1 <= M <= TUPLE_LOSS_MAX_NEG or B > 65535:
+        raise ValueError(f"{what}: 1 <= B <= 65535, 1 <= M <= {TUPLE_LOSS_MAX_NEG} and L >= 1 are supported (got {shapes})")
+    for name, t in (("anchors", anchors), ("positives", positives), ("negatives", negatives)):
+        if (L > 1 and t.stride(-1) != 1) or any(s < 0 for s in t.stride()):
+            raise ValueError(f"{what}: the last dimension of {name} must be contiguous (strides {t.stride()}; {shapes})")
+    return anchors.device, B, M, L
+
+
+def _tuple_strides(anchors, positives, negatives):
+    return (int(anchors.stride(0)), int(positives.stride(0)), int(negatives.stride(0)), int(negatives.stride(1)))
+
+
+def tuple_loss_forward(anchors: torch.Tensor, positives: torch.Tensor, negatives: torch.Tensor, kind: str,
+                       margin: float = 0.3, temp: float = 0.07, score: str = "sqdist"):
+    """oibl_tuple_loss_forward: -> (loss, a 0-dim fp32 tensor; coef [B][1+M] fp64, the table the backward consumes)."""
+    if kind not in LOSS_KINDS:
+        raise ValueError(f"tuple_loss: unknown loss {kind!r} (one of {sorted(LOSS_KINDS)})")
+    if score not in LOSS_SCORES:
+        raise ValueError(f"tuple_loss: unknown score {score!r} (one of {sorted(LOSS_SCORES)})")
+    dev, B, M, L = _tuple_rows("tuple_loss", anchors, positives, negatives)
+    sa, sp, snt, snr = _tuple_strides(anchors, positives, negatives)
+    lib = _lib.load()
+    ws = workspace(lib.oibl_tuple_loss_workspace_bytes(B, M), dev, "tuple_loss")
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    coef = torch.empty((B, 1 + M), dtype=torch.float64, device=dev)
+    _lib.check(lib.oibl_tuple_loss_forward(_ptr(anchors), sa, _ptr(positives), sp, _ptr(negatives), snt, snr, B, M, L,
+                                           LOSS_KINDS[kind], LOSS_SCORES[score], float(margin), float(temp),
+                                           _ptr(loss), _ptr(coef), _ptr(ws), ws.numel(), _stream(dev)),
+               "tuple_loss_forward")
+    return loss, coef
+
+
+def tuple_loss_backward(anchors: torch.Tensor, positives: torch.Tensor, negatives: torch.Tensor, coef: torch.Tensor,
+                        grad_loss: torch.Tensor, kind: str, score: str = "sqdist", want: Sequence[str] = ("a", "p", "n")):
+    """oibl_tuple_loss_backward: one launch -> (grad_anchors [B][L] | None, grad_positives [B][L] | None,
+    grad_negatives [B][M][L] | None), compact fp32, for the letters in `want`.  grad_loss is a device fp32 scalar."""
+    dev, B, M, L = _tuple_rows("tuple_loss_backward", anchors, positives, negatives)
+    want = tuple(want)
+    if not want or any(t not in ("a", "p", "n") for t in want):
+        raise ValueError(f"tuple_loss_backward: want must name some of 'a', 'p', 'n' (got {want!r})")
+    if coef.dtype != torch.float64 or tuple(coef.shape) != (B, 1 + M) or not coef.is_contiguous() or coef.device != dev:
+        raise ValueError(f"tuple_loss_backward: the table must be a contiguous float64 [{B}][{1 + M}] "
+                         f"(got {coef.dtype} {tuple(coef.shape)})")
+    if grad_loss.dtype != torch.float32 or grad_loss.numel() != 1 or grad_loss.device != dev:
+        raise ValueError(f"tuple_loss_backward: grad_loss must be one float32 on the device (got {grad_loss.dtype} "
+                         f"{tuple(grad_loss.shape)})")
+    sa, sp, snt, snr = _tuple_strides(anchors, positives, negatives)
+    ga = torch.empty((B, L), dtype=torch.float32, device=dev) if "a" in want else None
+    gp = torch.empty((B, L), dtype=torch.float32, device=dev) if "p" in want else None
+    gn = torch.empty((B, M, L), dtype=torch.float32, device=dev) if "n" in want else None
+    _lib.check(_lib.load().oibl_tuple_loss_backward(_ptr(anchors), sa, _ptr(positives), sp, _ptr(negatives), snt, snr,
+                                                    B, M, L, LOSS_KINDS[kind], LOSS_SCORES[score], _ptr(coef),
+                                                    _ptr(grad_loss), _ptr(ga), _ptr(gp), _ptr(gn), _stream(dev)),
+               "tuple_loss_backward")
+    return ga, gp, gn
+
+
+class _TupleLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, anchors, positives, negatives, kind, margin, temp, score):
+        loss, coef = tuple_loss_forward(anchors, positives, negatives, kind, margin=margin, temp=temp, score=score)
+        ctx.save_for_backward(anchors, positives, negatives, coef)
+        ctx.kind, ctx.score = kind, score
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_loss):
+        anchors, positives, negatives, coef = ctx.saved_tensors
+        want = tuple(t for t, n in zip(("a", "p", "n"), ctx.needs_input_grad[:3]) if n)
+        if not want:
+            return None, None, None, None, None, None, None
+        ga, gp, gn = tuple_loss_backward(anchors, positives, negatives, coef,
+                                         grad_loss.to(torch.float32).contiguous(), ctx.kind, ctx.score, want=want)
+        return ga, gp, gn, None, None, None, None
+
+
+def tuple_loss(anchors: torch.Tensor, positives: torch.Tensor, negatives: torch.Tensor, kind: str,
+               margin: float = 0.3, temp: float = 0.07, score: str = "sqdist") -> torch.Tensor:
+    """The tuple losses of the reference's trainers, fused (oibl_tuple_loss_forward / _backward): anchors [B][L],
+    positives [B][L], negatives [B][M][L] fp32, strided views read in place -> the scalar loss, with a graph to
+    whichever of the three requires a gradient.
+      kind 'triplet'     F.triplet_margin_loss(margin, p=2, reduction='mean') over the B M triples
+           'sare_joint'  (-log_softmax([z_pos, z_neg_1 ..], 1)[:, 0]).mean() over B
+           'sare_ind'    the same over the B M pairs [z_pos, z_neg_j]
+      score 'sqdist'     z = -|a - x|^2 (Trainer._get_loss)      'dot'  z = <a, x> / temp (SFRSTrainer._get_loss)
+    Two launches forward, one backward, fp64 inside, bit-identical from run to run."""
+    return _TupleLoss.apply(anchors, positives, negatives, kind, float(margin), float(temp), score)
+
+
+def _soft_rows(what: str, student: torch.Tensor, teacher: Optional[torch.Tensor]):
+    shapes = f"student {tuple(student.shape)}" + ("" if teacher is None else f", teacher {tuple(teacher.shape)}")
+    dev = _need_cuda(student, teacher)
+    if student.dim() != 2 or student.dtype != torch.float32 or (teacher is not None and (
+            teacher.shape != student.shape or teacher.dtype != torch.float32)):
+        raise ValueError(f"{what}: contiguous float32 [B][J] score tables of one shape are expected (got {shapes})")
+    B, J = map(int, student.shape)
+    if not 1 <= B <= 65535 or not 1 <= J <= SOFT_LABEL_MAX_J:
+        raise ValueError(f"{what}: 1 <= B <= 65535 and 1 <= J <= {SOFT_LABEL_MAX_J} are supported (got {shapes})")
+    return dev, B, J
+
+
+def soft_label_loss_forward(student: torch.Tensor, teacher: torch.Tensor, temp_student: float, temp_teacher: float):
+    """oibl_soft_label_loss_forward: -> (loss, 0-dim fp32; coef [B][J] fp64 = dloss / dstudent)."""
+    dev, B, J = _soft_rows("soft_label_loss", student, teacher)
+    if not (temp_student > 0 and temp_teacher > 0):
+        raise ValueError(f"soft_label_loss: temperatures must be positive (got {temp_student}, {temp_teacher})")
+    lib = _lib.load()
+    ws = workspace(lib.oibl_soft_label_loss_workspace_bytes(B, J), dev, "soft_label_loss")
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    coef = torch.empty((B, J), dtype=torch.float64, device=dev)
+    _lib.check(lib.oibl_soft_label_loss_forward(_ptr(student), _ptr(teacher), B, J, float(temp_student),
+                                                float(temp_teacher), _ptr(loss), _ptr(coef), _ptr(ws), ws.numel(),
+                                                _stream(dev)), "soft_label_loss_forward")
+    return loss, coef
+
+
+class _SoftLabelLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, student, teacher, temp_student, temp_teacher):
+        loss, coef = soft_label_loss_forward(student, teacher, temp_student, temp_teacher)
+        ctx.save_for_backward(coef)
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_loss):
+        (coef,) = ctx.saved_tensors
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None
+        B, J = map(int, coef.shape)
+        out = torch.empty((B, J), dtype=torch.float32, device=coef.device)
+        _lib.check(_lib.load().oibl_soft_label_loss_backward(_ptr(coef), B, J,
+                                                             _ptr(grad_loss.to(torch.float32).contiguous()),
+                                                             _ptr(out), _stream(coef.device)), "soft_label_loss_backward")
+        return out, None, None, None
+
+
+def soft_label_loss(student: torch.Tensor, teacher: torch.Tensor, temp_student: float, temp_teacher: float) -> torch.Tensor:
+    """loss_soft of SFRSTrainer._forward, fused: student, teacher [B][J] fp32 contiguous ->
+    (-softmax(teacher / temp_teacher, 1) * log_softmax(student / temp_student, 1)).mean(0).sum().  The teacher is a
+    label: it gets no gradient; the student's is (softmax(s / ts) - softmax(t / tt)) / (B ts), one launch."""
+    return _SoftLabelLoss.apply(student, teacher.detach(), float(temp_student), float(temp_teacher))
+
+
 # ---- PCA --------------------------------------------------------------------------------------
 class PcaWeight:
     """A PCA weight [d][D] resident on the device, with — fp32 only — the re-packed copy the streaming kernel
