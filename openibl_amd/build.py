@@ -39,16 +39,10 @@ CXXFLAGS = [
 ]
 
 
-# compile-time experiments ride in the DEBUG library only (a script times the same layer through the product
-# library and through this one: tests/gpu_dbgvariant_ab.py).  Round 4: ["-DOIBL_MX_TAIL_B128"] — the f16mx fragment
-# tail as one ds_read_b128 instead of b64 + b32 (same bits, 6.950 -> 6.936 ms over the layers: nothing; off again);
-# ["-DOIBL_RING_LGKM0"] — lgkmcnt(0) in front of every COMPUTE segment, the schedule before the counted waits.
-# Round 6: ["-DOIBL_STEM_R6_LDS"] — the f16mx stem with MX tails as one ds_read_b128 and conflict-free producer line
-# writes (2612 -> 452 modelled bank-conflict cycles per tile, 2.0e8 -> 3.5e7 measured per launch): not faster (1.609
-# against 1.598 ms — the kernel is bound by VALU issue: profiles/r06_d_stem_lds_ab.txt); not adopted, off again.
-# ["-DOIBL_STEM_SPLIT"] — the f16mx stem of rounds 3-5 (two workgroups per tile, resident weights) as the debug library:
-# tests/gpu_stem_lds_ab.py times it against the product (one workgroup per tile): 1.555 -> 1.384 ms, bit-identical,
-# profiles/r06_j_stem_dual_ab.txt — adopted; off again.  ["-DOIBL_HALO4_CONT"]: profiles/r06_e_halo4_cont.txt.
+# Compile-time experiments ride in the DEBUG library only: put the experiment behind a macro, name its -D flag here
+# and time the same layer through the product library and through this one (tests/gpu_dbgvariant_ab.py,
+# tests/gpu_stem_lds_ab.py).  An experiment that is settled leaves the tree; its measurement stays
+# (profiles/README.md lists the ones run this way).
 DBG_EXPERIMENT_FLAGS = []
 
 
@@ -213,7 +207,8 @@ def _build_locked(verbose: bool, force: bool = False) -> Path:
 
     def compile_one(job):
         src, obj, dbg = job
-        # an object whose source, headers and flags are unchanged is kept (conv.hip alone is two minutes of hipcc);
+        # an object whose source, headers and flags are unchanged is kept (conv.hip with its ring / halo instantiations
+        # is two minutes of hipcc, stem.hip a quarter of one);
         # its compiler remarks are kept next to it so that the resource report stays complete
         key, keyfile, remfile = _object_key(src, dbg), obj.with_suffix(".key"), obj.with_suffix(".remarks")
         if not force and obj.exists() and keyfile.exists() and remfile.exists() and keyfile.read_text() == key:
@@ -233,7 +228,8 @@ def _build_locked(verbose: bool, force: bool = False) -> Path:
 
     # the big translation units first, so that the pool is never left with one long job at the end
     jobs.sort(key=lambda j: -j[0].stat().st_size)
-    with ThreadPoolExecutor(max_workers=min(os.cpu_count() or 4, len(jobs))) as ex:
+    # (not os.cpu_count(): a shared machine shows all of its CPUs to a job that may use a few of them)
+    with ThreadPoolExecutor(max_workers=max(1, min(16, int(os.environ.get("MAX_JOBS", 16)), len(jobs)))) as ex:
         results = list(ex.map(compile_one, jobs))
     remarks = "\n".join(text for dbg, text in results if not dbg)
     (BUILD_DIR / "resource_usage.json").write_text(json.dumps(_parse_resource_usage(remarks), indent=1))

@@ -38,36 +38,6 @@
 // after the lgkmcnt(0) that closes every mma segment.  The halo is last read in P2 of tap 8 and overwritten behind
 // the barrier of P3.  Units beyond the last K-tile load an in-range line into a per-wave sink, so the counts
 // are constants.
-// -DOIBL_HALO4_CONT (debug library, round 6; VERDICT r05 item 3 "give the two workgroups of a CU a stagger discipline"):
-// a CONTINUOUS-ISSUE K loop instead of the phases below.
-// Rounds 5's phases were LOAD (ten fragment reads, wait) then MMA (six matrix instructions): with ONE wave per SIMD and
-// workgroup nothing covers a wave's own LOAD, and two uncoordinated workgroups per CU reached 57-68 % of the matrix
-// pipe inside the K loop (2260-2660 cycles per K-tile against 2 x 768).  Now a wave never stops issuing matrix
-// instructions to load: every A fragment is re-read for its NEXT use right behind the last instruction that reads it
-// (the order of halo4_mma6 leaves each reload five instructions = 160 pipe cycles before its first reader — the
-// discipline of the f16mx stem's consumers), and the B sets are read a whole phase ahead:
-//   P0  read B1(t) into the set B0(t-1) vacated                              mma  A0 x B0(t)
-//   P1  lgkmcnt(0); barrier SA; issue B0(t+2), B1(t+2) over K-tile t         mma  A0 x B1(t), A0 <- A1(tap) behind its readers
-//   P2                                                                        mma  A1 x B1(t)
-//   P3  vmcnt(2 NB); barrier SB; read B0(t+1) into the set B1(t) vacated     mma  A1 x B0(t), A1 <- A0(tap + 1) behind its readers
-//   chunk start (tap 0, not the first): vmcnt(0); barrier; read A0(tap 0)    — the halo has landed (tap 8 pre-reads
-//       nothing: the next chunk's halo is issued behind SB of tap 8 and overwrites the buffer the reads would hit)
-// Hazards.  RAW: K-tile t+1's units were issued behind SA(t-1); at SB(t) a wave allows only the 2 NB instructions of
-// K-tile t+2 (issued behind SA(t)) in flight, every wave crosses SB behind its own wait: B0(t+1) (read in P3(t)) and
-// B1(t+1) (read in P0(t+1)) have landed.  WAR: K-tile t's buffer is last read in P3(t-1) (B0) and P0(t) (B1); both
-// reads are retired by the lgkmcnt(0) in front of SA(t) — which P1's first instruction needs anyway — so the units
-// of K-tile t+2 issued behind SA(t) overwrite nothing a wave still reads.  Nothing is outstanding at SB (P1's A
-// reloads were consumed by P2), so neither barrier exposes an LDS latency.  The halo is last read in P1 of tap 8 (A1)
-// and overwritten behind SB of tap 8.  Units beyond the last K-tile load an in-range line into a per-wave sink, so
-// the counts are constants.  The MX operand's tail is read as ONE ds_read_b128 ([d4 d5 0 scale], scale = register 7):
-// with both workgroups issuing continuously the LDS port is the next limit, and the b64 + b32 tails' bank conflicts
-// (12 cycles instead of 4, tools/lds_stem_model.py) were a third of its read cycles.
-// Measured (one box, gpurun r06_e; profiles/r06_e_halo4_cont.txt): all 136 tests of test_gpu_mx / splitk / range green,
-// K loop + prologue per workgroup 45.5k -> 42.5k shader cycles on conv2_1 and 81.6k -> 79.0k on conv2_2 — and the
-// layers' WALL time unchanged (0.721 -> 0.721 ms, 1.010 -> 1.034 ms against an unchanged ring kernel on the same
-// boxes): these launches sit at the board's power cap (1.75-1.87 GHz of 2.4), where cycles saved on stalls come back as
-// a lower clock — what moves them is fewer joules per tile, not a tighter interleave.  256 VGPRs against
-// 239; the pooled variant parks ten values in scratch.  Not adopted: the product keeps the phases.
 #pragma once
 
 #include "conv_halo.h"
@@ -217,221 +187,6 @@ __global__ __launch_bounds__(H4_THREADS, 2) void conv3x3_halo4_kernel(HaloParams
   }
   const int row_pitch = HP * 128;
 
-#ifdef OIBL_HALO4_CONT
-  bf16x8_t fa[2][4], fbx[4], fby[4];
-  // (every piece of a fragment — fp16 k-halves, e2m3 dwords 0-3, the tail slot [d4 d5 0 scale] — is one 16-byte slot)
-  auto ld_frag = [&](const char* a) __attribute__((always_inline)) -> bf16x8_t {
-    return *reinterpret_cast<const bf16x8_t*>(a);
-  };
-  // the two row blocks' base addresses of A(h) at tap: fragment kk of block i2 is at a0[i2] ^ ((kk << 5) ^ cdy)
-  int a_cur[2];
-  auto a_base = [&](auto h_c, auto tap_c) __attribute__((always_inline)) {
-    constexpr int h = decltype(h_c)::value, tap = decltype(tap_c)::value;
-    constexpr int dyi = tap / 3, dxi = tap % 3;
-    int rp_ = row_pitch;
-    asm volatile("" : "+s"(rp_));     // (opaque: keeps 9 taps x 16 loop-invariant addresses out of scratch)
-    const int tapoff = dyi * rp_ + dxi * 128;
-#pragma unroll
-    for (int i2 = 0; i2 < 2; ++i2) {
-      a_cur[i2] = pre[h][i2][dxi];
-      asm volatile("" : "+v"(a_cur[i2]));
-      a_cur[i2] += tapoff;
-    }
-  };
-  auto ld_a = [&](auto tap_c, int i2, int kk) __attribute__((always_inline)) {
-    constexpr int tap = decltype(tap_c)::value;
-    constexpr int cdy = (tap / 3 != 1) ? 64 : 0;
-    fa[i2][kk] = ld_frag(smem + (a_cur[i2] ^ ((kk << 5) ^ cdy)));
-  };
-  auto read_a = [&](auto h_c, auto tap_c) __attribute__((always_inline)) {   // all of A(h) at once (prologue, chunk starts)
-    a_base(h_c, tap_c);
-#pragma unroll
-    for (int kk = 0; kk < 4; ++kk)
-#pragma unroll
-      for (int i2 = 0; i2 < 2; ++i2) ld_a(tap_c, i2, kk);
-  };
-  auto read_b = [&](int buf, int h, bf16x8_t (&f)[4]) __attribute__((always_inline)) {
-    const char* s = rd_b + buf * H4_B_TILE + h * H4_B_UNIT;
-#pragma unroll
-    for (int kk = 0; kk < 4; ++kk) f[kk] = ld_frag(s + frag_off[kk]);
-  };
-  // one phase: six matrix instructions on two accumulator tiles; after(q) runs right behind instruction q (the
-  // reloads of the fragments it was the last reader of).  sched_barrier pins the written order: left alone, the
-  // scheduler sinks every reload to just in front of its use (conv.hip, the f16mx stem's consumers).
-  auto mma6 = [&](f32x16_t& acc0, f32x16_t& acc1, const bf16x8_t (&fb)[4], auto&& after) __attribute__((always_inline)) {
-    typedef __attribute__((ext_vector_type(4))) int i4;
-    auto f16 = [&](f32x16_t& acc, int i2, int k) __attribute__((always_inline)) {
-      const f16x8_t a = __builtin_bit_cast(f16x8_t, fa[i2][k]), b = __builtin_bit_cast(f16x8_t, fb[k]);
-      acc = SWAP ? __builtin_amdgcn_mfma_f32_32x32x16_f16(b, a, acc, 0, 0, 0)
-                 : __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, acc, 0, 0, 0);
-    };
-    auto mx = [&](f32x16_t& acc, int i2) __attribute__((always_inline)) {
-      // (the tail slot's zero dword is never read: without a use the allocator hands that register to a temporary
-      //  while the ds_read_b128 that writes it is still in flight — and protects the temporary with an lgkmcnt(0) in
-      //  front of the phase's first matrix instruction, i.e. the exposed LOAD this schedule is there to remove)
-      asm volatile("" ::"v"(fa[i2][3]), "v"(fb[3]));
-      const i32x8_t a8 = __builtin_shufflevector(__builtin_bit_cast(i4, fa[i2][2]), __builtin_bit_cast(i4, fa[i2][3]),
-                                                 0, 1, 2, 3, 4, 5, 6, 7);
-      const i32x8_t b8 = __builtin_shufflevector(__builtin_bit_cast(i4, fb[2]), __builtin_bit_cast(i4, fb[3]), 0, 1, 2,
-                                                 3, 4, 5, 6, 7);
-      // e2m3 x e2m3 (cbsz = blgp = 2); scales: byte 0 of register 7 of either operand (the tail slot's last dword)
-      acc = SWAP ? __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(b8, a8, acc, 2, 2, 0, b8[7], 0, a8[7])
-                 : __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a8, b8, acc, 2, 2, 0, a8[7], 0, b8[7]);
-    };
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_setprio(1);
-    f16(acc0, 0, 0);
-    __builtin_amdgcn_sched_barrier(0);
-    after(0);
-    __builtin_amdgcn_sched_barrier(0);
-    f16(acc1, 1, 0);
-    __builtin_amdgcn_sched_barrier(0);
-    after(1);
-    __builtin_amdgcn_sched_barrier(0);
-    f16(acc0, 0, 1);
-    __builtin_amdgcn_sched_barrier(0);
-    after(2);
-    __builtin_amdgcn_sched_barrier(0);
-    f16(acc1, 1, 1);
-    __builtin_amdgcn_sched_barrier(0);
-    after(3);
-    __builtin_amdgcn_sched_barrier(0);
-    mx(acc0, 0);
-    __builtin_amdgcn_sched_barrier(0);
-    after(4);
-    __builtin_amdgcn_sched_barrier(0);
-    mx(acc1, 1);
-    __builtin_amdgcn_sched_barrier(0);
-    after(5);
-    asm volatile("" : "+v"(acc0), "+v"(acc1));  // pin the results inside the segment (ring_core.h)
-    __builtin_amdgcn_s_setprio(0);
-    __builtin_amdgcn_sched_barrier(0);
-  };
-  // the reload of A behind its readers: instruction q was the last reader of fa[q & 1][q >> 1] (q < 4), of
-  // fa[0][2..3] (q = 4), of fa[1][2..3] (q = 5)
-  auto reload_a = [&](auto tap_c, int q) __attribute__((always_inline)) {
-    if (q < 4) {
-      ld_a(tap_c, q & 1, q >> 1);
-    } else {
-      ld_a(tap_c, q - 4, 2);
-      ld_a(tap_c, q - 4, 3);
-    }
-  };
-  auto bar = [&]() __attribute__((always_inline)) {
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-  };
-
-  // accumulators start at the bias (conv_halo.h)
-  f32x16_t acc[4][2];
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    if constexpr (POOL) {
-      float b = p.bias[n0 + wn * 64 + j * 32 + (lane & 31)] * p.bias_mul;
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          asm volatile("" : "+v"(b));
-          acc[i][j][r] = b;
-        }
-    } else {
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        float4 b = *reinterpret_cast<const float4*>(p.bias + n0 + wn * 64 + j * 32 + 8 * g + 4 * (lane >> 5));
-        b = make_float4(b.x * p.bias_mul, b.y * p.bias_mul, b.z * p.bias_mul, b.w * p.bias_mul);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          acc[i][j][4 * g] = b.x;
-          acc[i][j][4 * g + 1] = b.y;
-          acc[i][j][4 * g + 2] = b.z;
-          acc[i][j][4 * g + 3] = b.w;
-        }
-      }
-    }
-  }
-
-  using I0 = std::integral_constant<int, 0>;
-  using I1 = std::integral_constant<int, 1>;
-  // ---- prologue: the halo of chunk 0, the weights of K-tiles 0 and 1; everything landed; B0(0) and A0(tap 0) read
-  stage_halo(0);
-  begin_tile();
-  stage_b(0, 0, true);
-  stage_b(0, 1, true);
-  begin_tile();
-  stage_b(1, 0, true);
-  stage_b(1, 1, true);
-  wait_vmcnt<0>();
-  bar();
-  read_b(0, 0, fbx);
-  read_a(I0{}, std::integral_constant<int, 0>{});
-
-#define H4_IC(x) std::integral_constant<int, (x)> {}
-  auto ktile = [&](auto par_c, auto tap_c, int cc, int kt) __attribute__((always_inline)) {
-    constexpr int PAR = decltype(par_c)::value;
-    constexpr int TAP = decltype(tap_c)::value;
-    constexpr int NXT = TAP == 8 ? 0 : TAP + 1;
-    bf16x8_t(&b0)[4] = PAR ? fby : fbx;
-    bf16x8_t(&b1)[4] = PAR ? fbx : fby;
-    const bool more = kt + 2 < nk;
-    if constexpr (TAP == 0) {
-      if (kt > 0) {          // a new chunk: its halo (issued behind SB of the previous tap 8) has landed
-        wait_vmcnt<0>();
-        bar();
-        read_a(I0{}, tap_c);
-      }
-    }
-    // P0: A0 x B0; B1(t) arrives under it
-    read_b(PAR, 1, b1);
-    mma6(acc[0][0], acc[1][0], b0, [&](int q) __attribute__((always_inline)) {
-      if (q == 1) begin_tile();   // (scalar cursor of the K-tile staged in P1, in the shadow of the matrix pipe)
-    });
-    // P1: A0 x B1; A1(tap) behind A0's readers.  SA: every wave's reads of K-tile t's buffer are retired
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    bar();
-    stage_b(PAR, 0, more);    // K-tile t + 2 over K-tile t
-    stage_b(PAR, 1, more);
-    a_base(I1{}, tap_c);
-    mma6(acc[0][1], acc[1][1], b1, [&](int q) __attribute__((always_inline)) { reload_a(tap_c, q); });
-    // P2: A1 x B1
-    mma6(acc[2][1], acc[3][1], b1, [](int) __attribute__((always_inline)) {});
-    // P3: A1 x B0; B0(t+1) into the set B1 vacated; A0(tap + 1) behind A1's readers.  SB: K-tile t+1 has landed
-    wait_vmcnt<2 * NB>();
-    bar();
-    read_b(PAR ^ 1, 0, b1);
-    if constexpr (TAP == 8) {
-      if (cc + 1 < chunks) stage_halo(cc + 1);     // (over the halo A1(tap 8) was the last to read: no pre-read of A0)
-      mma6(acc[2][0], acc[3][0], b0, [](int) __attribute__((always_inline)) {});
-    } else {
-      a_base(I0{}, H4_IC(NXT));
-      mma6(acc[2][0], acc[3][0], b0, [&](int q) __attribute__((always_inline)) { reload_a(H4_IC(NXT), q); });
-    }
-  };
-  for (int cc = 0; cc < chunks; cc += 2) {
-    const int kt = 9 * cc;
-    ktile(I0{}, H4_IC(0), cc, kt);
-    ktile(I1{}, H4_IC(1), cc, kt + 1);
-    ktile(I0{}, H4_IC(2), cc, kt + 2);
-    ktile(I1{}, H4_IC(3), cc, kt + 3);
-    ktile(I0{}, H4_IC(4), cc, kt + 4);
-    ktile(I1{}, H4_IC(5), cc, kt + 5);
-    ktile(I0{}, H4_IC(6), cc, kt + 6);
-    ktile(I1{}, H4_IC(7), cc, kt + 7);
-    ktile(I0{}, H4_IC(8), cc, kt + 8);
-    ktile(I1{}, H4_IC(0), cc + 1, kt + 9);
-    ktile(I0{}, H4_IC(1), cc + 1, kt + 10);
-    ktile(I1{}, H4_IC(2), cc + 1, kt + 11);
-    ktile(I0{}, H4_IC(3), cc + 1, kt + 12);
-    ktile(I1{}, H4_IC(4), cc + 1, kt + 13);
-    ktile(I0{}, H4_IC(5), cc + 1, kt + 14);
-    ktile(I1{}, H4_IC(6), cc + 1, kt + 15);
-    ktile(I0{}, H4_IC(7), cc + 1, kt + 16);
-    ktile(I1{}, H4_IC(8), cc + 1, kt + 17);
-  }
-#undef H4_IC
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // (the last P3's pre-read of a K-tile that does not exist)
-#else
   bf16x8_t fa[2][4], fbx[4], fby[4];
   auto ld_frag = [&](const char* a, int kk) __attribute__((always_inline)) -> bf16x8_t {
     if (kk == 3) {
@@ -574,7 +329,6 @@ __global__ __launch_bounds__(H4_THREADS, 2) void conv3x3_halo4_kernel(HaloParams
     ktile(I1{}, H4_IC(8), cc + 1, kt + 17);
   }
 #undef H4_IC
-#endif
   wait_vmcnt<0>();  // (sink writes of the last dummies)
   __syncthreads();
   if (wgprof) p.prof[64 + 4 * (size_t)blockIdx.x + 3] = __builtin_amdgcn_s_memtime();

@@ -47,7 +47,7 @@ struct RingParams {
   int raster;   // xcd_tile() mode
   int korder;   // 0 = (tap, channel chunk), 1 = (channel chunk, tap): see ConvRingALoader::begin_tile
   unsigned* range_flag;  // f16mx output: raised when an output is beyond fp16 (common.h, mx_raise_range_flag); may be null
-  // Activation scale of the f16mx backbone (conv.hip, g_mx_act_shift): the accumulators start at bias * bias_mul, and
+  // Activation scale of the f16mx backbone (vgg.hip, g_mx_act_shift): the accumulators start at bias * bias_mul, and
   // out_mul != 1 (the layer that hands the fp32 map to the head) multiplies them once behind the loop.  Both 1
   // for a stand-alone layer.
   float bias_mul = 1.f, out_mul = 1.f;
@@ -218,20 +218,6 @@ struct ConvRingBLoader {
       if (i >= i0 && i < i1) buf_glds16(rsrc, off[NB * h + i], soff, dst + i * 8192);
   }
 };
-
-// (hi, lo) pairs of four fp32 values as two dwords each: hi = bf16(v), lo = bf16(v - hi)
-__device__ static inline void ring_split4(float a0, float a1, float a2, float a3, uint2& hi, uint2& lo) {
-  typedef __attribute__((ext_vector_type(2))) float f2;
-  typedef __attribute__((ext_vector_type(2))) __bf16 bf2;
-  hi.x = __builtin_bit_cast(uint32_t, __builtin_convertvector((f2){a0, a1}, bf2));
-  hi.y = __builtin_bit_cast(uint32_t, __builtin_convertvector((f2){a2, a3}, bf2));
-  const float r0 = a0 - __builtin_bit_cast(float, hi.x << 16);
-  const float r1 = a1 - __builtin_bit_cast(float, hi.x & 0xffff0000u);
-  const float r2 = a2 - __builtin_bit_cast(float, hi.y << 16);
-  const float r3 = a3 - __builtin_bit_cast(float, hi.y & 0xffff0000u);
-  lo.x = __builtin_bit_cast(uint32_t, __builtin_convertvector((f2){r0, r1}, bf2));
-  lo.y = __builtin_bit_cast(uint32_t, __builtin_convertvector((f2){r2, r3}, bf2));
-}
 
 // OUTMX: the output is written as f16mx lines (always with f16mx operands; the parameter exists because the
 // epilogue only depends on it: bf16x3 operands with f16mx output compile too — round 3 ran conv2_1 that way
@@ -528,7 +514,7 @@ __device__ __forceinline__ void conv3x3_ring_body(const RingParams& p, char* sme
       typedef __attribute__((ext_vector_type(2))) float f2;
       typedef __attribute__((ext_vector_type(2))) __bf16 bf2;
       typedef __attribute__((ext_vector_type(2))) short s2;
-      // ReLU on the packed pair: as signed 16-bit integers every negative bf16 is < 0 (see conv.hip)
+      // ReLU on the packed pair: as signed 16-bit integers every negative bf16 is < 0 (see stem.hip, relu_bf16x2)
       const short fl = p.relu ? (short)0 : (short)-32768;
       const s2 floor2 = {fl, fl};
       const int half = lane >> 5;

@@ -1,7 +1,6 @@
 // Query x gallery squared-L2 distance matrix and per-row top-k on gfx950.
 // Reference behaviour: pairwise_distance (ibl/evaluators.py:105-130) and the argsort consumed by
 // evaluate_all (ibl/evaluators.py:142-159).
-#undef OIBL_MX_TAIL_B128   // the distance kernels have no registers for the 16-byte tail (ring_core.h)
 #include "gemm_core.h"
 #include "ring_core.h"
 

@@ -126,6 +126,20 @@ __device__ static inline void buf_glds16(__amdgpu_buffer_rsrc_t rsrc, unsigned v
       rsrc, (__attribute__((address_space(3))) void*)lds_wave_base, 16, (int)voff, (int)soff, 0, 0);
 }
 
+// (hi, lo) pairs of four fp32 values as two dwords each: hi = bf16(v), lo = bf16(v - hi)
+__device__ static inline void ring_split4(float a0, float a1, float a2, float a3, uint2& hi, uint2& lo) {
+  typedef __attribute__((ext_vector_type(2))) float f2;
+  typedef __attribute__((ext_vector_type(2))) __bf16 bf2;
+  hi.x = __builtin_bit_cast(uint32_t, __builtin_convertvector((f2){a0, a1}, bf2));
+  hi.y = __builtin_bit_cast(uint32_t, __builtin_convertvector((f2){a2, a3}, bf2));
+  const float r0 = a0 - __builtin_bit_cast(float, hi.x << 16);
+  const float r1 = a1 - __builtin_bit_cast(float, hi.x & 0xffff0000u);
+  const float r2 = a2 - __builtin_bit_cast(float, hi.y << 16);
+  const float r3 = a3 - __builtin_bit_cast(float, hi.y & 0xffff0000u);
+  lo.x = __builtin_bit_cast(uint32_t, __builtin_convertvector((f2){r0, r1}, bf2));
+  lo.y = __builtin_bit_cast(uint32_t, __builtin_convertvector((f2){r2, r3}, bf2));
+}
+
 template <int N>
 __device__ static inline void wait_vmcnt() {
   static_assert(N >= 0 && N < 64, "vmcnt is a 6-bit field");
@@ -233,7 +247,6 @@ __device__ static inline void ring_mainloop(f32x16_t (&acc)[4][2], char* smem, i
   // (coalesced by the allocator); with a b128 tail the operand had to be re-assembled by copies into
   // fresh registers, ~20 VGPRs the distance kernels do not have.
   auto read_frag = [&](const char* s, int kk) __attribute__((always_inline)) -> bf16x8_t {
-#ifndef OIBL_MX_TAIL_B128
     if constexpr (MX) {
       if (kk == 3) {
         // (an ext_vector load, not HIP's uint2 struct: a struct load carries no TBAA, and the compiler
@@ -245,7 +258,6 @@ __device__ static inline void ring_mainloop(f32x16_t (&acc)[4][2], char* smem, i
         return __builtin_bit_cast(bf16x8_t, (u4){d.x, d.y, sc, 0u});
       }
     }
-#endif
     return *reinterpret_cast<const bf16x8_t*>(s + frag_off[kk]);
   };
   auto read_a = [&](int buf, int h) __attribute__((always_inline)) {
@@ -254,18 +266,11 @@ __device__ static inline void ring_mainloop(f32x16_t (&acc)[4][2], char* smem, i
     // Fragments in the order the MFMAs consume them (k-chunk outer), and NO lgkmcnt(0) in front of COMPUTE:
     // the compiler's own counted waits (lgkmcnt(9), (8), (7), (6), (2), (0) in an f16mx A phase) let the first
     // MFMAs start while the tails are still in flight.  +1.5 % on the f16mx layers, nothing in bf16, same bits
-    // (profiles/r04_h_lgkm_ab.txt; OIBL_RING_LGKM0 restores the row-outer order and the full wait).
-#ifndef OIBL_RING_LGKM0
+    // (profiles/r04_h_lgkm_ab.txt, against the row-outer order behind a full lgkmcnt(0)).
 #pragma unroll
     for (int kk = 0; kk < 4; ++kk)
 #pragma unroll
       for (int i2 = 0; i2 < 2; ++i2) fa[i2][kk] = read_frag(s + i2 * 4096, kk);
-#else
-#pragma unroll
-    for (int i2 = 0; i2 < 2; ++i2)
-#pragma unroll
-      for (int kk = 0; kk < 4; ++kk) fa[i2][kk] = read_frag(s + i2 * 4096, kk);
-#endif
   };
   auto read_b = [&](int buf, int h, bf16x8_t (&f)[4]) __attribute__((always_inline)) {
     if constexpr (P == RING_MX_NOREAD) return;
@@ -276,9 +281,6 @@ __device__ static inline void ring_mainloop(f32x16_t (&acc)[4][2], char* smem, i
 
   auto compute = [&](auto h_c, auto j_c, const bf16x8_t (&fb)[4], auto&& issue) __attribute__((always_inline)) {
     constexpr int h = decltype(h_c)::value, j = decltype(j_c)::value;
-#ifdef OIBL_RING_LGKM0
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#endif
     __builtin_amdgcn_sched_barrier(0);
     if constexpr (BAR1 && GROUP == 0) {   // both groups compute inside one barrier interval: the one that still
       __builtin_amdgcn_s_setprio(2);      // has to LOAD goes first
@@ -311,11 +313,7 @@ __device__ static inline void ring_mainloop(f32x16_t (&acc)[4][2], char* smem, i
         const i32x8_t a8 = __builtin_shufflevector(__builtin_bit_cast(i4, fa[i2][2]),
                                                    __builtin_bit_cast(i4, fa[i2][3]), 0, 1, 2, 3, 4, 5, 6, 7);
         // e2m3 x e2m3 (cbsz = blgp = 2); scales: byte 0 of dword 6 of either operand
-#ifdef OIBL_MX_TAIL_B128
-        constexpr int SC = 7;   // the tail slot read as one ds_read_b128: [d4 d5 0 scale]
-#else
         constexpr int SC = 6;
-#endif
         acc[2 * h + i2][j] =
             SWAP ? __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(b8, a8, acc[2 * h + i2][j], 2, 2, 0, b8[SC], 0, a8[SC])
                  : __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a8, b8, acc[2 * h + i2][j], 2, 2, 0, a8[SC], 0, b8[SC]);

@@ -177,7 +177,7 @@ class VGG(_PrecisionMixin, nn.Module):
         """Images of h x w one f16mx pass takes: its kernels address their input through 32-bit buffer offsets and have
         no other implementation — the largest activation they read (conv2_2's input, [N][H/2][W/2][128] 4-byte
         elements: 39 MB per 480x640 image) and the stem's fp32 input must stay below 3.5 GB (vgg16_f16mx_fits in
-        csrc/conv.hip is the same test; the C entry point refuses what this lets through): 94 images of 480x640."""
+        csrc/vgg.hip is the same test; the C entry point refuses what this lets through): 94 images of 480x640."""
         per = max(3 * h * w * 4, (h // 2) * (w // 2) * 128 * 4, 1)
         return (0xE0000000 - 1) // per
 

@@ -1,8 +1,11 @@
-"""The f16mx stem of this build (product library: MX tails as ds_read_b64 + ds_read_b32, producer lane = halo pixel)
-against the debug library compiled with -DOIBL_STEM_R6_LDS (openibl_amd/build.py, DBG_EXPERIMENT_FLAGS: tails as one
-ds_read_b128, producer lanes on even / odd pixels — the conflict-free LDS pattern of tools/lds_stem_model.py): time per
-launch at batch 32 x 480x640, alternating, and bit-identity of the outputs (diagnostic, not a pytest).
-    python tests/gpu_stem_lds_ab.py [rounds]          (profiles/r06_d_stem_lds_ab.txt: run with the roles swapped)"""
+"""The f16mx stem of this build (product library) against the debug library compiled with an experiment macro of the
+stem (openibl_amd/build.py, DBG_EXPERIMENT_FLAGS): time per launch at batch 32 x 480x640, alternating, and bit-identity
+of the outputs (diagnostic, not a pytest).
+    python tests/gpu_stem_lds_ab.py [rounds]
+Run this way: the conflict-free LDS pattern of tools/lds_stem_model.py — MX tails as one ds_read_b128, producer lanes on
+even / odd pixels — against b64 + b32 tails and lane = pixel (profiles/r06_d_stem_lds_ab.txt, roles swapped: not faster
+on the two-workgroup kernel), and one workgroup per tile against two (profiles/r06_j_stem_dual_ab.txt: adopted, with
+that pattern; the macros have left the tree)."""
 import sys
 from pathlib import Path
 

@@ -17,8 +17,8 @@ w1 = torch.randn((64, 3, 3, 3), generator=g, device=dev) * 0.27
 b1 = torch.randn((64,), generator=g, device=dev) * 0.1
 w2 = torch.randn((64, 64, 3, 3), generator=g, device=dev) * 0.06
 b2 = torch.randn((64,), generator=g, device=dev) * 0.1
-tiles = N * ((H + 7) // 8) * ((W + 31) // 32) / 128    # per workgroup, two workgroups per tile (bf16x3; f16mx with -DOIBL_STEM_SPLIT)
-tiles_mx = N * ((H + 7) // 8) * ((W + 31) // 32) / 256  # f16mx, one workgroup per tile (round 6): 256 tile streams
+tiles = N * ((H + 7) // 8) * ((W + 31) // 32) / 128    # per workgroup, two workgroups per tile (bf16x3)
+tiles_mx = N * ((H + 7) // 8) * ((W + 31) // 32) / 256  # f16mx, one workgroup per tile: 256 tile streams
 modes = [int(a) for a in sys.argv[1:] if not a.startswith("--")] or [0]
 for name, fn, prec, mode in [("bf16x3", ops.vgg16_stem_x3, "bf16x3", 0)] + [("f16mx", ops.vgg16_stem_mx, "f16mx", m) for m in modes]:
     L.oibl_debug_set_stem3_prio(mode)   # producer priority | consumer priority << 2

@@ -74,7 +74,7 @@ def test_one_layer_at_three_magnitudes(dev, cin, cout, pool, xpeak, wgain, over)
     assert_rel_l2("bf16x3 layer", ops.x3_join(g3).permute(0, 3, 1, 2).cpu(), want, 1e-5)
 
 
-# The f16mx backbone stores its activations multiplied by 2^-3 (conv.hip, g_mx_act_shift): the fp16 bound sits at
+# The f16mx backbone stores its activations multiplied by 2^-3 (vgg.hip, g_mx_act_shift): the fp16 bound sits at
 # 65504 * 8 = 5.2e5 in activation units.
 ACT_HEADROOM = 8.0
 

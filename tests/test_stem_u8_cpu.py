@@ -1,4 +1,4 @@
-"""uint8 input of the bf16x3 / f16mx stems (csrc/conv.hip, vgg_stem_x3_kernel<MX, U8>), the parts that can be
+"""uint8 input of the bf16x3 / f16mx stems (csrc/stem.hip, vgg_stem_x3_kernel<MX, U8>), the parts that can be
 checked without a GPU:
 
 1. Normalize as ONE fma, v = u * a_c + b_c, against the loader's three rounded fp32 operations
