@@ -18,9 +18,10 @@
 //   where a max(., eps) is active its denominator is a constant (torch's clamp_min): the projection term is dropped.
 //
 // The reference keeps residual[N][K][C][P] for autograd (157 MB per 30 x 40 image); nothing of that size exists
-// here.  The call is stateless: it recomputes r, a and V from the map, then
+// here.  The call is stateless: it recomputes r, a and V from the map, then (the bodies of the chunk kernels, the
+// aggregation and the reduction are vlad_backward_core.h's, instantiated with PlainMap: a unit is an image)
 //   nvb_assign_kernel        one workgroup per (32-pixel chunk, image): the chunk's 32 x 512 values in LDS, |x_p| and
-//                            the logits in fp64 on the vector unit (see the kernel: its a is a more accurate
+//                            the logits in fp64 on the vector unit (see vlad_assign: its a is a more accurate
 //                            evaluation than the forward kernels', not their bits), softmax      -> r[P], a[P][64]
 //   nvb_aggregate_kernel<0>  netvlad_aggregate_kernel's scheme on v_mfma_f32_32x32x2_f32, one workgroup per (image,
 //                            64 channels), all the image's pixels in order; A in fp64            -> V[K][C], A[K]
@@ -39,301 +40,34 @@
 // feeds dC is wider: a tuple loss's dL/dY sum to zero over a tuple, so the images' dC contributions cancel (60-fold
 // on near-identical maps) and every fp32 rounding of a contribution is multiplied by that factor — the logits, the
 // norms, the normalisations' backward and the per-image dC are therefore fp64.
-#include "gemm_core.h"
+#include "vlad_backward_core.h"
 
 namespace oibl {
 
-constexpr int NVB_C = 512;
-constexpr int NVB_K = 64;
-constexpr int NVB_XP = 516;          // floats per LDS row of the chunk: 16-byte aligned, +4 banks per pixel
-constexpr int NVB_LP = 65;           // pitch of the [32][64] partial tiles
-constexpr int NVB_AP = 129;          // pitch of the [32][128] operand tile [a | ds]
-constexpr int NVB_CONTRACT_LDS = (32 * NVB_XP + 4 * 32 * NVB_LP + 32) * 4;
-constexpr int NVB_DX_LDS = (32 * NVB_XP + 32 * NVB_AP + 4 * 32 + 32 + 32) * 4;
-constexpr float NVB_EPS = 1e-12f;
+constexpr int NVB_ASSIGN_LDS = VLB_ASSIGN_LDS + PlainMap::TABLE_BYTES;
+constexpr int NVB_CONTRACT_LDS = VLB_CONTRACT_LDS + PlainMap::TABLE_BYTES;
+constexpr int NVB_DX_LDS = VLB_DX_LDS + PlainMap::TABLE_BYTES;
 
-__device__ static inline double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-// the chunk [p0, p0 + 32) of one image -> x_s[32][NVB_XP]; pixels beyond P read as zeros
-__device__ static inline void nvb_load_chunk(const float* __restrict__ fimg, int p0, int P, float* x_s) {
-#pragma unroll
-  for (int q = 0; q < 16; ++q) {
-    const int idx = (int)threadIdx.x + 256 * q;          // float4 index inside the chunk
-    const int px = idx >> 7, c4 = (idx & 127) * 4;
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (p0 + px < P) v = *reinterpret_cast<const float4*>(fimg + (size_t)(p0 + px) * NVB_C + c4);
-    *reinterpret_cast<float4*>(x_s + px * NVB_XP + c4) = v;
-  }
-}
-
-// rn[p] = |x_p| (1 without normalize) and a[p][k] = softmax_k(w_k . x_p / r_p) for one 32-pixel chunk of one image.
-// The logits and the norm are accumulated in fp64 on the vector unit, not on the fp32 matrix cores: a tuple loss makes
-// the images' contributions to dC cancel (60-fold on near-identical maps), and the rounding of fp32 logits alone —
-// 512-term sums whose terms are far larger than the sum — then costs 8e-7 to 3e-6 of dC.  This `a` is therefore NOT
-// the forward kernels' `a` bit for bit (netvlad.hip forms its logits on the fp32 matrix cores): the backward
-// differentiates the same function from a more accurate evaluation of it.  Eight threads per pixel, thread `sub`
-// the clusters sub, sub + 8, ..., sub + 56; the weights pass through LDS in four slices of 128 channels, [cluster]
-// [channel] as in memory (coalesced 512-byte row pieces in, the eight rows of a wave's reads on distinct banks).
-constexpr int NVB_WP = 132;          // floats per LDS row of the weight slice: 16-byte aligned, +4 banks per cluster
-constexpr int NVB_ASSIGN_LDS = (32 * NVB_XP + NVB_K * NVB_WP) * 4;
+// one workgroup per (32-pixel chunk, image): grid (chunks, N)
 __global__ __launch_bounds__(256) void nvb_assign_kernel(const float* __restrict__ feat, const float* __restrict__ w,
                                                          float* __restrict__ rn, float* __restrict__ a, int P,
                                                          int normalize) {
-  constexpr int C = NVB_C;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* const x_s = reinterpret_cast<float*>(smem);             // [32][NVB_XP]
-  float* const w_s = x_s + 32 * NVB_XP;                           // [64 clusters][NVB_WP]: 128 channels of a slice
-  const int n = blockIdx.y, p0 = blockIdx.x * 32;
-  const int px = (int)threadIdx.x >> 3, sub = (int)threadIdx.x & 7;
-  nvb_load_chunk(feat + (size_t)n * P * C, p0, P, x_s);
-  double acc[8], ss = 0.0;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) acc[j] = 0.0;
-  for (int c0 = 0; c0 < C; c0 += 128) {
-    __syncthreads();                                              // the chunk is in LDS / the last slice is consumed
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-      const int idx = (int)threadIdx.x + 256 * q;
-      const int c4 = idx & 31, k = idx >> 5;                      // k < 64; 32 lanes walk one row's 512 bytes
-      *reinterpret_cast<float4*>(w_s + k * NVB_WP + 4 * c4) =
-          *reinterpret_cast<const float4*>(w + (size_t)k * C + c0 + 4 * c4);
-    }
-    __syncthreads();
-    const float* xr = x_s + px * NVB_XP + c0;
-    const float* wr = w_s + sub * NVB_WP;
-#pragma unroll 2
-    for (int c = 0; c < 128; c += 4) {
-      const float4 xv = *reinterpret_cast<const float4*>(xr + c);
-      const double x0 = (double)xv.x, x1 = (double)xv.y, x2 = (double)xv.z, x3 = (double)xv.w;
-      ss = fma(x0, x0, ss);
-      ss = fma(x1, x1, ss);
-      ss = fma(x2, x2, ss);
-      ss = fma(x3, x3, ss);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const float4 wv = *reinterpret_cast<const float4*>(wr + 8 * j * NVB_WP + c);
-        acc[j] = fma(x0, (double)wv.x, acc[j]);
-        acc[j] = fma(x1, (double)wv.y, acc[j]);
-        acc[j] = fma(x2, (double)wv.z, acc[j]);
-        acc[j] = fma(x3, (double)wv.w, acc[j]);
-      }
-    }
-  }
-  const double rd = normalize ? sqrt(ss) : 1.0;
-  const double invd = 1.0 / fmax(rd, (double)NVB_EPS);
-  float l[8], mx = -INFINITY;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    l[j] = (float)(acc[j] * invd);
-    mx = fmaxf(mx, l[j]);
-  }
-  mx = fmaxf(mx, __shfl_xor(mx, 1, 64));
-  mx = fmaxf(mx, __shfl_xor(mx, 2, 64));
-  mx = fmaxf(mx, __shfl_xor(mx, 4, 64));
-  float ssum = 0.f;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    l[j] = expf(l[j] - mx);
-    ssum += l[j];
-  }
-  ssum += __shfl_xor(ssum, 1, 64);
-  ssum += __shfl_xor(ssum, 2, 64);
-  ssum += __shfl_xor(ssum, 4, 64);
-  const float is = 1.0f / ssum;
-  if (p0 + px < P) {
-    float* dst = a + ((size_t)n * P + p0 + px) * NVB_K + sub;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) dst[8 * j] = l[j] * is;         // the eight threads of a pixel: 32 bytes per j
-    if (sub == 0) rn[(size_t)n * P + p0 + px] = (float)rd;
-  }
+  vlad_assign(PlainMap{P}, feat, w, rn, a, normalize);
 }
 
-// ds[p][k] = a_pk (da_pk - sum_j a_pj da_pj), da_pk = dV_k . x_p / r_p - dvc_k, for one 32-pixel chunk of one image:
-// the chunk in LDS, every wave contracts its 128 channels against the image's dV on v_mfma_f32_32x32x2_f32, the four
-// partial [32 x 64] tiles are added through LDS.  `out` may alias `a` (every element is read and written by the same
-// thread).
 __global__ __launch_bounds__(256) void nvb_contract_kernel(const float* __restrict__ feat, const float* __restrict__ B,
                                                            const float* __restrict__ dvc, const float* __restrict__ rn,
                                                            const float* a, float* out, int P) {
-  constexpr int C = NVB_C;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* const x_s = reinterpret_cast<float*>(smem);             // [32][NVB_XP]
-  float* const lp_s = x_s + 32 * NVB_XP;                          // [4 waves][32][NVB_LP]
-  float* const inv_s = lp_s + 4 * 32 * NVB_LP;                    // [32]
-  const int n = blockIdx.y, p0 = blockIdx.x * 32;
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int l31 = lane & 31, kh = lane >> 5;
-  const float* fimg = feat + (size_t)n * P * C;
-  B += (size_t)n * NVB_K * C;
-
-  nvb_load_chunk(fimg, p0, P, x_s);
-  if (threadIdx.x < 32) {
-    const int p = p0 + (int)threadIdx.x;
-    inv_s[threadIdx.x] = p < P ? 1.0f / fmaxf(rn[(size_t)n * P + p], NVB_EPS) : 0.f;
-  }
-  __syncthreads();
-  {  // partial contraction over this wave's 128 channels: [32 pixels] x [64 rows of B]
-    f32x16_t lg[2];
-#pragma unroll
-    for (int ct = 0; ct < 2; ++ct)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) lg[ct][r] = 0.f;
-    const float* xa = x_s + l31 * NVB_XP + 128 * wave + 4 * kh;
-    const float* wb = B + (size_t)l31 * C + 128 * wave + 4 * kh;
-#pragma unroll 4
-    for (int j = 0; j < 16; ++j) {
-      const float4 av = *reinterpret_cast<const float4*>(xa + 8 * j);
-      const float4 b0 = *reinterpret_cast<const float4*>(wb + 8 * j);
-      const float4 b1 = *reinterpret_cast<const float4*>(wb + (size_t)32 * C + 8 * j);
-      lg[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, b0.x, lg[0], 0, 0, 0);
-      lg[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, b1.x, lg[1], 0, 0, 0);
-      lg[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, b0.y, lg[0], 0, 0, 0);
-      lg[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, b1.y, lg[1], 0, 0, 0);
-      lg[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.z, b0.z, lg[0], 0, 0, 0);
-      lg[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.z, b1.z, lg[1], 0, 0, 0);
-      lg[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, b0.w, lg[0], 0, 0, 0);
-      lg[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, b1.w, lg[1], 0, 0, 0);
-    }
-    float* lw = lp_s + wave * 32 * NVB_LP;
-#pragma unroll
-    for (int ct = 0; ct < 2; ++ct)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) lw[acc_row(r, lane) * NVB_LP + 32 * ct + l31] = lg[ct][r];
-  }
-  __syncthreads();
-  {  // eight threads per pixel, eight clusters each
-    const int px = (int)threadIdx.x >> 3, sub = (int)threadIdx.x & 7;
-    const float iv = inv_s[px];
-    const bool live = p0 + px < P;
-    float l[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const int o = px * NVB_LP + sub * 8 + k;
-      l[k] = (lp_s[o] + lp_s[32 * NVB_LP + o] + lp_s[2 * 32 * NVB_LP + o] + lp_s[3 * 32 * NVB_LP + o]) * iv;
-    }
-    float* dst = out + ((size_t)n * P + p0 + px) * NVB_K + sub * 8;
-    {
-      float av[8];
-#pragma unroll
-      for (int k = 0; k < 8; ++k) av[k] = 0.f;
-      if (live) {
-        const float* src = a + ((size_t)n * P + p0 + px) * NVB_K + sub * 8;
-        const float4 a0 = *reinterpret_cast<const float4*>(src), a1 = *reinterpret_cast<const float4*>(src + 4);
-        av[0] = a0.x; av[1] = a0.y; av[2] = a0.z; av[3] = a0.w;
-        av[4] = a1.x; av[5] = a1.y; av[6] = a1.z; av[7] = a1.w;
-      }
-      float dot = 0.f;
-#pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        l[k] -= dvc[n * NVB_K + sub * 8 + k];
-        dot = fmaf(av[k], l[k], dot);
-      }
-      dot += __shfl_xor(dot, 1, 64);
-      dot += __shfl_xor(dot, 2, 64);
-      dot += __shfl_xor(dot, 4, 64);
-      if (live) {
-        *reinterpret_cast<float4*>(dst) = make_float4(av[0] * (l[0] - dot), av[1] * (l[1] - dot),
-                                                      av[2] * (l[2] - dot), av[3] * (l[3] - dot));
-        *reinterpret_cast<float4*>(dst + 4) = make_float4(av[4] * (l[4] - dot), av[5] * (l[5] - dot),
-                                                          av[6] * (l[6] - dot), av[7] * (l[7] - dot));
-      }
-    }
-  }
+  vlad_contract(PlainMap{P}, feat, B, dvc, rn, a, out);
 }
 
-// out[n][k][c0..c0+63] = sum_p a[p][k] xh[p][c] for one image and one 64-channel slice, the pixels in order.
-// MODE 0: minus (sum_p a[p][k]) centroids[k][c], and A[n][k] = sum_p a[p][k] (every slice computes the same sums
-// in the same order; slice 0 writes them).  MODE 1: the plain sum (a = ds: the image's dW).
-// 4 waves as 2 (clusters) x 2 (channels), one 32x32 fp32 accumulator tile each.
+// one workgroup per (image, 64 channels): one segment per image, all its P pixels
 template <int MODE>
 __global__ __launch_bounds__(256) void nvb_aggregate_kernel(const float* __restrict__ feat,
                                                             const float* __restrict__ rn, const float* __restrict__ a,
                                                             const float* __restrict__ centroids,
                                                             float* __restrict__ out, double* __restrict__ A, int P) {
-  constexpr int C = NVB_C;
-  __shared__ __attribute__((aligned(16))) float a_s[32][64];
-  __shared__ __attribute__((aligned(16))) float x_s[32][64];
-  __shared__ float s_sum[64];
-  const int n = blockIdx.x, c0 = blockIdx.y * 64;
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int wm = wave >> 1, wn = wave & 1;
-  const float* fbase = feat + (size_t)n * P * C + c0;
-  const float* abase = a + (size_t)n * P * 64;
-  const float* rbase = rn + (size_t)n * P;
-
-  f32x16_t acc;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-  double colsum = 0.0;  // threads 0..63: sum_p a[p][tid], in fp64 (1200 terms of a 30 x 40 map)
-
-  // staging roles: a chunk = 32 x 64 floats = 512 float4 (2 per thread); x chunk = 32 pixels x 64 channels
-  // (8 threads per pixel, 8 channels each).  The next chunk's loads are issued before the current chunk's MFMAs.
-  const int xp = threadIdx.x >> 3, xc = (threadIdx.x & 7) * 8;
-  float4 pa[2], px0, px1;
-  float psc;
-  auto prefetch = [&](int p0) __attribute__((always_inline)) {
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-      const int idx = threadIdx.x + q * 256;  // float4 index
-      const int pr = idx >> 4, cq = (idx & 15) * 4;
-      pa[q] = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (p0 + pr < P) pa[q] = *reinterpret_cast<const float4*>(abase + (size_t)(p0 + pr) * 64 + cq);
-    }
-    px0 = make_float4(0.f, 0.f, 0.f, 0.f);
-    px1 = px0;
-    psc = 0.f;
-    if (p0 + xp < P) {
-      psc = 1.0f / fmaxf(rbase[p0 + xp], NVB_EPS);
-      const float* src = fbase + (size_t)(p0 + xp) * C + xc;
-      px0 = *reinterpret_cast<const float4*>(src);
-      px1 = *reinterpret_cast<const float4*>(src + 4);
-    }
-  };
-  prefetch(0);
-  for (int p0 = 0; p0 < P; p0 += 32) {
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-      const int idx = threadIdx.x + q * 256;
-      *reinterpret_cast<float4*>(&a_s[idx >> 4][(idx & 15) * 4]) = pa[q];
-    }
-    *reinterpret_cast<float4*>(&x_s[xp][xc]) = make_float4(px0.x * psc, px0.y * psc, px0.z * psc, px0.w * psc);
-    *reinterpret_cast<float4*>(&x_s[xp][xc + 4]) = make_float4(px1.x * psc, px1.y * psc, px1.z * psc, px1.w * psc);
-    __syncthreads();
-    if (p0 + 32 < P) prefetch(p0 + 32);
-    if (MODE == 0 && threadIdx.x < 64) {
-#pragma unroll
-      for (int p = 0; p < 32; ++p) colsum += (double)a_s[p][threadIdx.x];
-    }
-#pragma unroll
-    for (int s = 0; s < 16; ++s) {
-      const int p = 2 * s + (lane >> 5);
-      const float av = a_s[p][wm * 32 + (lane & 31)];
-      const float bv = x_s[p][wn * 32 + (lane & 31)];
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc, 0, 0, 0);
-    }
-    __syncthreads();
-  }
-  if (MODE == 0) {
-    if (threadIdx.x < 64) {
-      s_sum[threadIdx.x] = (float)colsum;
-      if (blockIdx.y == 0) A[n * 64 + threadIdx.x] = colsum;
-    }
-    __syncthreads();
-  }
-  const int ch = c0 + wn * 32 + (lane & 31);
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int k = wm * 32 + acc_row(r, lane);
-    float v = acc[r];
-    if (MODE == 0) v -= s_sum[k] * centroids[(size_t)k * C + ch];
-    out[((size_t)n * 64 + k) * C + ch] = v;
-  }
+  vlad_aggregate<MODE>(PlainMap{P}, feat, rn, a, centroids, out, A, 1, P);
 }
 
 // one wave per (image, cluster) row of V: st[row] = { |V_k| , |U_k|^2 , <U_k, G_k> }, U_k = V_k / max(|V_k|, eps).
@@ -342,7 +76,7 @@ __global__ __launch_bounds__(256) void nvb_aggregate_kernel(const float* __restr
 // multiplies every fp32 rounding of a contribution by that factor.
 __global__ __launch_bounds__(256) void nvb_rowstats_kernel(const float* __restrict__ V, const float* __restrict__ G,
                                                            double* __restrict__ st, long rows) {
-  constexpr int C = NVB_C;
+  constexpr int C = VLB_C;
   const int lane = threadIdx.x & 63;
   const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
@@ -361,7 +95,7 @@ __global__ __launch_bounds__(256) void nvb_rowstats_kernel(const float* __restri
   for (int i = 0; i < 8; ++i) ss += vv[i] * vv[i];
   ss = wave_sum_f64(ss);
   const double t = sqrt(ss);
-  const double it = 1.0 / fmax(t, (double)NVB_EPS);
+  const double it = 1.0 / fmax(t, (double)VLB_EPS);
   double s2 = 0.0, ug = 0.0;
 #pragma unroll
   for (int i = 0; i < 8; ++i) {
@@ -384,7 +118,7 @@ __global__ __launch_bounds__(256) void nvb_dv_kernel(float* __restrict__ V, cons
                                                      const double* __restrict__ st, const double* __restrict__ A,
                                                      const float* __restrict__ centroids, float* __restrict__ dvc,
                                                      double* __restrict__ dCp, long rows) {
-  constexpr int C = NVB_C, K = NVB_K;
+  constexpr int C = VLB_C, K = VLB_K;
   const int lane = threadIdx.x & 63;
   const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
@@ -394,12 +128,12 @@ __global__ __launch_bounds__(256) void nvb_dv_kernel(float* __restrict__ V, cons
   const double S2 = wave_sum_f64(st[3 * (n * K + lane) + 1]);
   const double UG = wave_sum_f64(st[3 * (n * K + lane) + 2]);
   const double gn = sqrt(S2);
-  const bool g_clamped = gn < (double)NVB_EPS;
-  const double ig = 1.0 / fmax(gn, (double)NVB_EPS);
+  const bool g_clamped = gn < (double)VLB_EPS;
+  const double ig = 1.0 / fmax(gn, (double)VLB_EPS);
   const double yg = g_clamped ? 0.0 : UG * ig;                      // <Y, G>; a clamped g is a constant
   const double t = st[3 * row];
-  const bool t_clamped = t < (double)NVB_EPS;
-  const double it = 1.0 / fmax(t, (double)NVB_EPS);
+  const bool t_clamped = t < (double)VLB_EPS;
+  const double it = 1.0 / fmax(t, (double)VLB_EPS);
   float* v = V + row * C;
   const float* g = G + row * C;
   const float* c = centroids + (size_t)k * C;
@@ -443,124 +177,16 @@ __global__ __launch_bounds__(256) void nvb_dv_kernel(float* __restrict__ V, cons
   if (lane == 0) dvc[row] = (float)dc;
 }
 
-// grad_feat of one 32-pixel chunk of one image: dxh[p][c] = sum_k a[p][k] dV[k][c] + sum_k ds[p][k] w[k][c], every
-// wave its 128 channels (4 accumulator tiles of 32 pixels x 32 channels, 128 contraction steps), then
-// dx_p = (dxh_p - xh_p <xh_p, dxh_p>) / r_p.
 __global__ __launch_bounds__(256) void nvb_dx_kernel(const float* __restrict__ feat, const float* __restrict__ rn,
                                                      const float* __restrict__ a, const float* __restrict__ ds,
                                                      const float* __restrict__ dV, const float* __restrict__ w,
                                                      float* __restrict__ grad_feat, int P, int normalize) {
-  constexpr int C = NVB_C;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* const x_s = reinterpret_cast<float*>(smem);             // [32][NVB_XP]
-  float* const ad_s = x_s + 32 * NVB_XP;                          // [32][NVB_AP]: a | ds
-  float* const red_s = ad_s + 32 * NVB_AP;                        // [4 waves][32]
-  float* const inv_s = red_s + 4 * 32;                            // [32]
-  float* const dot_s = inv_s + 32;                                // [32]
-  const int n = blockIdx.y, p0 = blockIdx.x * 32;
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int l31 = lane & 31, kh = lane >> 5;
-  const float* fimg = feat + (size_t)n * P * C;
-  dV += (size_t)n * NVB_K * C;
-
-  nvb_load_chunk(fimg, p0, P, x_s);
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {                                   // 32 x 128 floats = 1024 float4
-    const int idx = (int)threadIdx.x + 256 * q;
-    const int px = idx >> 5, k4 = (idx & 31) * 4;                 // k4 < 64: a, else ds
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (p0 + px < P) {
-      const float* src = (k4 < 64 ? a : ds) + ((size_t)n * P + p0 + px) * NVB_K + (k4 & 63);
-      v = *reinterpret_cast<const float4*>(src);
-    }
-    float* d = ad_s + px * NVB_AP + k4;
-    d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
-  }
-  if (threadIdx.x < 32) {
-    const int p = p0 + (int)threadIdx.x;
-    inv_s[threadIdx.x] = p < P ? 1.0f / fmaxf(rn[(size_t)n * P + p], NVB_EPS) : 0.f;
-    // the projection is dropped where the input is not normalised or its norm sits on the clamp
-    dot_s[threadIdx.x] = 0.f;
-  }
-  __syncthreads();
-
-  f32x16_t acc[4];
-#pragma unroll
-  for (int ct = 0; ct < 4; ++ct)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[ct][r] = 0.f;
-  const float* arow = ad_s + l31 * NVB_AP + kh;
-  const int cb = 128 * wave + l31;
-#pragma unroll 1
-  for (int half = 0; half < 2; ++half) {
-    const float* Bm = (half == 0 ? dV : w) + (size_t)kh * C + cb;
-    const float* ar = arow + 64 * half;
-#pragma unroll 4
-    for (int s = 0; s < 32; ++s) {
-      const float av = ar[2 * s];
-      const float* br = Bm + (size_t)(2 * s) * C;
-#pragma unroll
-      for (int ct = 0; ct < 4; ++ct)
-        acc[ct] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, br[32 * ct], acc[ct], 0, 0, 0);
-    }
-  }
-  if (normalize) {
-    // <x_p, dxh_p>: this wave's 128 channels, then the four waves in wave order
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int px = acc_row(r, lane);
-      float v = 0.f;
-#pragma unroll
-      for (int ct = 0; ct < 4; ++ct) v = fmaf(acc[ct][r], x_s[px * NVB_XP + cb + 32 * ct], v);
-      v += __shfl_xor(v, 16, 64);
-      v += __shfl_xor(v, 8, 64);
-      v += __shfl_xor(v, 4, 64);
-      v += __shfl_xor(v, 2, 64);
-      v += __shfl_xor(v, 1, 64);
-      if (l31 == 0) red_s[wave * 32 + px] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < 32) {
-      const int p = p0 + (int)threadIdx.x;
-      const float iv = inv_s[threadIdx.x];
-      const bool clamped = p < P ? rn[(size_t)n * P + p] < NVB_EPS : true;
-      const float d = ((red_s[threadIdx.x] + red_s[32 + threadIdx.x]) + red_s[64 + threadIdx.x]) + red_s[96 + threadIdx.x];
-      dot_s[threadIdx.x] = clamped ? 0.f : d * iv * iv;         // <xh_p, dxh_p> / r_p: it multiplies x_p below
-    }
-    __syncthreads();
-  }
-  float* gimg = grad_feat + (size_t)n * P * C;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int px = acc_row(r, lane);
-    if (p0 + px < P) {
-      const float iv = inv_s[px], d = dot_s[px];
-#pragma unroll
-      for (int ct = 0; ct < 4; ++ct) {
-        const int ch = cb + 32 * ct;
-        gimg[(size_t)(p0 + px) * C + ch] = (acc[ct][r] - x_s[px * NVB_XP + ch] * d) * iv;
-      }
-    }
-  }
+  vlad_dx(PlainMap{P}, feat, rn, a, ds, dV, w, grad_feat, normalize);
 }
 
-// dW = sum_n dWp[n] (fp32), dC = sum_n dCp[n] (fp64, rounded once), both in image order; either output may be null
 __global__ __launch_bounds__(256) void nvb_reduce_kernel(const float* __restrict__ dWp, const double* __restrict__ dCp,
                                                          float* __restrict__ dW, float* __restrict__ dC, int N) {
-  constexpr int KC = NVB_K * NVB_C;
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= KC) return;
-  if (dW) {
-    float s = 0.f;
-    for (int n = 0; n < N; ++n) s += dWp[(size_t)n * KC + i];
-    dW[i] = s;
-  }
-  if (dC) {
-    double s = 0.0;
-    for (int n = 0; n < N; ++n) s += dCp[(size_t)n * KC + i];
-    dC[i] = (float)s;
-  }
+  vlad_reduce(dWp, dCp, dW, dC, N);
 }
 
 }  // namespace oibl
@@ -569,33 +195,10 @@ using namespace oibl;
 
 extern "C" {
 
-// workspace: r [N][P] | a [N][P][64] | V -> dV [N][K][C] | stats [N][K][3] fp64 | A [N][K] fp64 | dvc [N][K] |
-//            dW of every image [N][K][C] | dC of every image [N][K][C] fp64 |
-//            ds [N][P][64] (only with grad_feat: without it ds overwrites a)
-static size_t nvb_off_a(int N, int P) { return align_up((size_t)N * P * sizeof(float), 256); }
-static size_t nvb_off_v(int N, int P) { return nvb_off_a(N, P) + align_up((size_t)N * P * 64 * sizeof(float), 256); }
-static size_t nvb_off_st(int N, int P, int K, int C) {
-  return nvb_off_v(N, P) + align_up((size_t)N * K * C * sizeof(float), 256);
-}
-static size_t nvb_off_A(int N, int P, int K, int C) {
-  return nvb_off_st(N, P, K, C) + align_up((size_t)N * K * 3 * sizeof(double), 256);
-}
-static size_t nvb_off_dvc(int N, int P, int K, int C) {
-  return nvb_off_A(N, P, K, C) + align_up((size_t)N * K * sizeof(double), 256);
-}
-static size_t nvb_off_dwp(int N, int P, int K, int C) {
-  return nvb_off_dvc(N, P, K, C) + align_up((size_t)N * K * sizeof(float), 256);
-}
-static size_t nvb_off_dcp(int N, int P, int K, int C) {
-  return nvb_off_dwp(N, P, K, C) + align_up((size_t)N * K * C * sizeof(float), 256);
-}
-static size_t nvb_off_ds(int N, int P, int K, int C) {
-  return nvb_off_dcp(N, P, K, C) + align_up((size_t)N * K * C * sizeof(double), 256);
-}
-
+// workspace: vlad_backward_layout with one unit (the image) and one normalised vector per image
 size_t oibl_netvlad_backward_workspace_bytes(int N, int P, int K, int C, int want_grad_feat) {
-  if (N <= 0 || P <= 0 || K != NVB_K || C != NVB_C) return 0;
-  return nvb_off_ds(N, P, K, C) + (want_grad_feat ? align_up((size_t)N * P * 64 * sizeof(float), 256) : 0);
+  if (N <= 0 || P <= 0 || K != VLB_K || C != VLB_C) return 0;
+  return vlad_backward_layout(N, P, 1, 1, want_grad_feat).total;
 }
 
 int oibl_netvlad_backward(const void* feat, int N, int P, int K, int C, int precision, const float* assign_w,
@@ -605,8 +208,8 @@ int oibl_netvlad_backward(const void* feat, int N, int P, int K, int C, int prec
   OIBL_REQUIRE(feat && assign_w && centroids && grad_vlad_norm && ws, "netvlad_backward: null pointer");
   OIBL_REQUIRE(grad_assign_w || grad_centroids || grad_feat, "netvlad_backward: no output requested");
   OIBL_REQUIRE(precision == OIBL_F32, "netvlad_backward: the feature map must be fp32 (got precision %d)", precision);
-  OIBL_REQUIRE(K == NVB_K, "netvlad_backward: kernels are built for num_clusters = 64 (got %d)", K);
-  OIBL_REQUIRE(C == NVB_C, "netvlad_backward: kernels are built for dim = 512 (got %d)", C);
+  OIBL_REQUIRE(K == VLB_K, "netvlad_backward: kernels are built for num_clusters = 64 (got %d)", K);
+  OIBL_REQUIRE(C == VLB_C, "netvlad_backward: kernels are built for dim = 512 (got %d)", C);
   OIBL_REQUIRE(N > 0 && P > 0, "netvlad_backward: bad shape N=%d P=%d", N, P);
   OIBL_REQUIRE(N <= 65535, "netvlad_backward: at most 65535 images per call (got %d)", N);
   OIBL_REQUIRE((uintptr_t)feat % 16 == 0 && (uintptr_t)assign_w % 16 == 0 && (uintptr_t)centroids % 16 == 0 &&
@@ -624,15 +227,16 @@ int oibl_netvlad_backward(const void* feat, int N, int P, int K, int C, int prec
   hipStream_t st = (hipStream_t)stream;
   char* wsb = (char*)ws;
   const float* x = (const float*)feat;
+  const VladBackwardLayout lay = vlad_backward_layout(N, P, 1, 1, grad_feat != nullptr);
   float* rn = (float*)wsb;
-  float* a = (float*)(wsb + nvb_off_a(N, P));
-  float* V = (float*)(wsb + nvb_off_v(N, P));
-  double* stats = (double*)(wsb + nvb_off_st(N, P, K, C));
-  double* A = (double*)(wsb + nvb_off_A(N, P, K, C));
-  float* dvc = (float*)(wsb + nvb_off_dvc(N, P, K, C));
-  float* dWp = (float*)(wsb + nvb_off_dwp(N, P, K, C));
-  double* dCp = grad_centroids ? (double*)(wsb + nvb_off_dcp(N, P, K, C)) : nullptr;
-  float* ds = grad_feat ? (float*)(wsb + nvb_off_ds(N, P, K, C)) : a;
+  float* a = (float*)(wsb + lay.a);
+  float* V = (float*)(wsb + lay.v);
+  double* stats = (double*)(wsb + lay.stats);
+  double* A = (double*)(wsb + lay.A);
+  float* dvc = (float*)(wsb + lay.dvc);
+  float* dWp = (float*)(wsb + lay.dwp);
+  double* dCp = grad_centroids ? (double*)(wsb + lay.dcp) : nullptr;
+  float* ds = grad_feat ? (float*)(wsb + lay.ds) : a;
   const dim3 pgrid((unsigned)((P + 31) / 32), (unsigned)N);
   const long vrows = (long)N * K;
   const unsigned rgrid = (unsigned)((vrows + 3) / 4);
@@ -666,7 +270,7 @@ int oibl_netvlad_backward(const void* feat, int N, int P, int K, int C, int prec
     OIBL_LAUNCH_CHECK();
   }
   if (grad_assign_w || grad_centroids) {
-    hipLaunchKernelGGL(nvb_reduce_kernel, dim3(NVB_K * NVB_C / 256), dim3(256), 0, st, (const float*)dWp,
+    hipLaunchKernelGGL(nvb_reduce_kernel, dim3(VLB_K * VLB_C / 256), dim3(256), 0, st, (const float*)dWp,
                        (const double*)dCp, grad_assign_w, grad_centroids, N);
     OIBL_LAUNCH_CHECK();
   }

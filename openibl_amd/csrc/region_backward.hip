@@ -23,6 +23,10 @@
 // residual[N*4][K][C][P/4] exists.  The workspace orders an image's pixels QUARTER-MAJOR (index j = q Pq + i, i the
 // row-major index inside quarter q of Pq = h/2 w/2 pixels); a chunk is 32 consecutive pixels of ONE quarter, so a
 // chunk has one dV.  A pixel is 2 KB contiguous in the NHWC map, so the gather costs no coalescing.
+//
+// The chunk kernels, the aggregation and the reduction are vlad_backward_core.h's bodies, the ones the plain head
+// runs, instantiated with QuarterMap: a unit is a quarter (m = 4 n + q), the grid is (4 N, chunks), and a 32-entry
+// table in LDS names the chunk's map pixels.
 //   rgb_assign_kernel        one workgroup per (quarter, chunk): |x_p| and the logits in fp64    -> r, a[j][64]
 //   rgb_aggregate_kernel<0>  one workgroup per (quarter, 64 channels), the quarter's pixels in order on
 //                            v_mfma_f32_32x32x2_f32; A in fp64                                   -> V_q[K][C], A_q[K]
@@ -41,327 +45,45 @@
 // and an image's grad_feat rows do not depend on its batch mates.  V / dW, da and dxh are exact fp32 on the matrix
 // cores; what feeds dC (logits, norms, both normalisations' backward, the per-image dC) is fp64 for the reason given
 // in netvlad_backward.hip: the loss_soft and tuple-loss gradients sum to zero over a tuple, the images' dC cancel.
-//
-// The chunk kernels repeat netvlad_backward.hip's bodies instead of sharing them through a header: that file's
-// outputs are pinned bit for bit, and the two differ in how a pixel index becomes an address, which dV a chunk
-// contracts against and which grid axis carries the image (4 N quarters do not fit a grid's y).
-#include "gemm_core.h"
+#include "vlad_backward_core.h"
 
 namespace oibl {
 
-constexpr int RGB_C = 512;
-constexpr int RGB_K = 64;
-constexpr int RGB_XP = 516;          // floats per LDS row of the chunk: 16-byte aligned, +4 banks per pixel
-constexpr int RGB_LP = 65;           // pitch of the [32][64] partial tiles
-constexpr int RGB_AP = 129;          // pitch of the [32][128] operand tile [a | ds]
-constexpr int RGB_WP = 132;          // floats per LDS row of the weight slice
-constexpr int RGB_ASSIGN_LDS = (32 * RGB_XP + RGB_K * RGB_WP + 32) * 4;
-constexpr int RGB_CONTRACT_LDS = (32 * RGB_XP + 4 * 32 * RGB_LP + 32 + 32) * 4;
-constexpr int RGB_DX_LDS = (32 * RGB_XP + 32 * RGB_AP + 4 * 32 + 32 + 32 + 32) * 4;
-constexpr float RGB_EPS = 1e-12f;
+constexpr int RGB_ASSIGN_LDS = VLB_ASSIGN_LDS + QuarterMap::TABLE_BYTES;
+constexpr int RGB_CONTRACT_LDS = VLB_CONTRACT_LDS + QuarterMap::TABLE_BYTES;
+constexpr int RGB_DX_LDS = VLB_DX_LDS + QuarterMap::TABLE_BYTES;
+
 // the quarters of the 9 regions as bit masks
 __device__ constexpr int RGB_MEMBERS[9] = {0xF, 0x3, 0xC, 0x5, 0xA, 0x1, 0x2, 0x4, 0x8};
 
-__device__ static inline double rgb_wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-// the map pixel (row-major in the h x w map) of pixel i of quarter q
-__device__ static inline int rgb_map_pixel(int q, int i, int hq, int wq) {
-  const int row = i / wq, col = i - row * wq;
-  return ((q >> 1) * hq + row) * (2 * wq) + (q & 1) * wq + col;
-}
-
-// pix_s[t] = map pixel of pixel p0 + t of quarter q, -1 beyond the quarter (threads 0..31; the caller synchronises)
-__device__ static inline void rgb_chunk_pixels(int q, int p0, int hq, int wq, int* pix_s) {
-  if (threadIdx.x < 32) {
-    const int i = p0 + (int)threadIdx.x;
-    pix_s[threadIdx.x] = i < hq * wq ? rgb_map_pixel(q, i, hq, wq) : -1;
-  }
-}
-
-// the 32 pixels named by pix_s of one image -> x_s[32][RGB_XP]; pixels beyond the quarter read as zeros
-__device__ static inline void rgb_load_chunk(const float* __restrict__ fimg, const int* pix_s, float* x_s) {
-#pragma unroll
-  for (int q = 0; q < 16; ++q) {
-    const int idx = (int)threadIdx.x + 256 * q;          // float4 index inside the chunk
-    const int px = idx >> 7, c4 = (idx & 127) * 4;
-    const int mp = pix_s[px];
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (mp >= 0) v = *reinterpret_cast<const float4*>(fimg + (size_t)mp * RGB_C + c4);
-    *reinterpret_cast<float4*>(x_s + px * RGB_XP + c4) = v;
-  }
-}
-
-// nvb_assign_kernel on one chunk of one quarter: rn[j] = |x_p| (1 without normalize), a[j][k] = softmax_k(w_k . xh_p),
-// norm and logits accumulated in fp64 on the vector unit.  blockIdx.x = 4 n + q, blockIdx.y the chunk.
+// one workgroup per (quarter, chunk): blockIdx.x = 4 n + q, blockIdx.y the chunk
 __global__ __launch_bounds__(256) void rgb_assign_kernel(const float* __restrict__ feat, const float* __restrict__ w,
                                                          float* __restrict__ rn, float* __restrict__ a, int hq, int wq,
                                                          int normalize) {
-  constexpr int C = RGB_C;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* const x_s = reinterpret_cast<float*>(smem);             // [32][RGB_XP]
-  float* const w_s = x_s + 32 * RGB_XP;                           // [64 clusters][RGB_WP]: 128 channels of a slice
-  int* const pix_s = reinterpret_cast<int*>(w_s + RGB_K * RGB_WP);  // [32]
-  const int Pq = hq * wq;
-  const int m = blockIdx.x, p0 = blockIdx.y * 32;
-  const int px = (int)threadIdx.x >> 3, sub = (int)threadIdx.x & 7;
-  rgb_chunk_pixels(m & 3, p0, hq, wq, pix_s);
-  __syncthreads();
-  rgb_load_chunk(feat + (size_t)(m >> 2) * 4 * Pq * C, pix_s, x_s);
-  double acc[8], ss = 0.0;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) acc[j] = 0.0;
-  for (int c0 = 0; c0 < C; c0 += 128) {
-    __syncthreads();                                              // the chunk is in LDS / the last slice is consumed
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-      const int idx = (int)threadIdx.x + 256 * q;
-      const int c4 = idx & 31, k = idx >> 5;
-      *reinterpret_cast<float4*>(w_s + k * RGB_WP + 4 * c4) =
-          *reinterpret_cast<const float4*>(w + (size_t)k * C + c0 + 4 * c4);
-    }
-    __syncthreads();
-    const float* xr = x_s + px * RGB_XP + c0;
-    const float* wr = w_s + sub * RGB_WP;
-#pragma unroll 2
-    for (int c = 0; c < 128; c += 4) {
-      const float4 xv = *reinterpret_cast<const float4*>(xr + c);
-      const double x0 = (double)xv.x, x1 = (double)xv.y, x2 = (double)xv.z, x3 = (double)xv.w;
-      ss = fma(x0, x0, ss);
-      ss = fma(x1, x1, ss);
-      ss = fma(x2, x2, ss);
-      ss = fma(x3, x3, ss);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const float4 wv = *reinterpret_cast<const float4*>(wr + 8 * j * RGB_WP + c);
-        acc[j] = fma(x0, (double)wv.x, acc[j]);
-        acc[j] = fma(x1, (double)wv.y, acc[j]);
-        acc[j] = fma(x2, (double)wv.z, acc[j]);
-        acc[j] = fma(x3, (double)wv.w, acc[j]);
-      }
-    }
-  }
-  const double rd = normalize ? sqrt(ss) : 1.0;
-  const double invd = 1.0 / fmax(rd, (double)RGB_EPS);
-  float l[8], mx = -INFINITY;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    l[j] = (float)(acc[j] * invd);
-    mx = fmaxf(mx, l[j]);
-  }
-  mx = fmaxf(mx, __shfl_xor(mx, 1, 64));
-  mx = fmaxf(mx, __shfl_xor(mx, 2, 64));
-  mx = fmaxf(mx, __shfl_xor(mx, 4, 64));
-  float ssum = 0.f;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    l[j] = expf(l[j] - mx);
-    ssum += l[j];
-  }
-  ssum += __shfl_xor(ssum, 1, 64);
-  ssum += __shfl_xor(ssum, 2, 64);
-  ssum += __shfl_xor(ssum, 4, 64);
-  const float is = 1.0f / ssum;
-  if (p0 + px < Pq) {
-    const size_t j = (size_t)m * Pq + p0 + px;
-    float* dst = a + j * RGB_K + sub;
-#pragma unroll
-    for (int jj = 0; jj < 8; ++jj) dst[8 * jj] = l[jj] * is;
-    if (sub == 0) rn[j] = (float)rd;
-  }
+  vlad_assign(QuarterMap{hq, wq}, feat, w, rn, a, normalize);
 }
 
-// nvb_contract_kernel on one chunk of one quarter against that quarter's dV (B[m]): ds[j][k].  `out` may alias `a`.
 __global__ __launch_bounds__(256) void rgb_contract_kernel(const float* __restrict__ feat, const float* __restrict__ B,
                                                            const float* __restrict__ dvc, const float* __restrict__ rn,
                                                            const float* a, float* out, int hq, int wq) {
-  constexpr int C = RGB_C;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* const x_s = reinterpret_cast<float*>(smem);             // [32][RGB_XP]
-  float* const lp_s = x_s + 32 * RGB_XP;                          // [4 waves][32][RGB_LP]
-  float* const inv_s = lp_s + 4 * 32 * RGB_LP;                    // [32]
-  int* const pix_s = reinterpret_cast<int*>(inv_s + 32);          // [32]
-  const int Pq = hq * wq;
-  const int m = blockIdx.x, p0 = blockIdx.y * 32;
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int l31 = lane & 31, kh = lane >> 5;
-  B += (size_t)m * RGB_K * C;
-
-  rgb_chunk_pixels(m & 3, p0, hq, wq, pix_s);
-  if (threadIdx.x < 32) {
-    const int p = p0 + (int)threadIdx.x;
-    inv_s[threadIdx.x] = p < Pq ? 1.0f / fmaxf(rn[(size_t)m * Pq + p], RGB_EPS) : 0.f;
-  }
-  __syncthreads();
-  rgb_load_chunk(feat + (size_t)(m >> 2) * 4 * Pq * C, pix_s, x_s);
-  __syncthreads();
-  {  // partial contraction over this wave's 128 channels: [32 pixels] x [64 rows of B]
-    f32x16_t lg[2];
-#pragma unroll
-    for (int ct = 0; ct < 2; ++ct)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) lg[ct][r] = 0.f;
-    const float* xa = x_s + l31 * RGB_XP + 128 * wave + 4 * kh;
-    const float* wb = B + (size_t)l31 * C + 128 * wave + 4 * kh;
-#pragma unroll 4
-    for (int j = 0; j < 16; ++j) {
-      const float4 av = *reinterpret_cast<const float4*>(xa + 8 * j);
-      const float4 b0 = *reinterpret_cast<const float4*>(wb + 8 * j);
-      const float4 b1 = *reinterpret_cast<const float4*>(wb + (size_t)32 * C + 8 * j);
-      lg[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, b0.x, lg[0], 0, 0, 0);
-      lg[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, b1.x, lg[1], 0, 0, 0);
-      lg[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, b0.y, lg[0], 0, 0, 0);
-      lg[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, b1.y, lg[1], 0, 0, 0);
-      lg[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.z, b0.z, lg[0], 0, 0, 0);
-      lg[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.z, b1.z, lg[1], 0, 0, 0);
-      lg[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, b0.w, lg[0], 0, 0, 0);
-      lg[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, b1.w, lg[1], 0, 0, 0);
-    }
-    float* lw = lp_s + wave * 32 * RGB_LP;
-#pragma unroll
-    for (int ct = 0; ct < 2; ++ct)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) lw[acc_row(r, lane) * RGB_LP + 32 * ct + l31] = lg[ct][r];
-  }
-  __syncthreads();
-  {  // eight threads per pixel, eight clusters each
-    const int px = (int)threadIdx.x >> 3, sub = (int)threadIdx.x & 7;
-    const float iv = inv_s[px];
-    const bool live = p0 + px < Pq;
-    float l[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const int o = px * RGB_LP + sub * 8 + k;
-      l[k] = (lp_s[o] + lp_s[32 * RGB_LP + o] + lp_s[2 * 32 * RGB_LP + o] + lp_s[3 * 32 * RGB_LP + o]) * iv;
-    }
-    const size_t off = ((size_t)m * Pq + p0 + px) * RGB_K + sub * 8;
-    float av[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) av[k] = 0.f;
-    if (live) {
-      const float4 a0 = *reinterpret_cast<const float4*>(a + off), a1 = *reinterpret_cast<const float4*>(a + off + 4);
-      av[0] = a0.x; av[1] = a0.y; av[2] = a0.z; av[3] = a0.w;
-      av[4] = a1.x; av[5] = a1.y; av[6] = a1.z; av[7] = a1.w;
-    }
-    float dot = 0.f;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      l[k] -= dvc[(size_t)m * RGB_K + sub * 8 + k];
-      dot = fmaf(av[k], l[k], dot);
-    }
-    dot += __shfl_xor(dot, 1, 64);
-    dot += __shfl_xor(dot, 2, 64);
-    dot += __shfl_xor(dot, 4, 64);
-    if (live) {
-      *reinterpret_cast<float4*>(out + off) = make_float4(av[0] * (l[0] - dot), av[1] * (l[1] - dot),
-                                                          av[2] * (l[2] - dot), av[3] * (l[3] - dot));
-      *reinterpret_cast<float4*>(out + off + 4) = make_float4(av[4] * (l[4] - dot), av[5] * (l[5] - dot),
-                                                              av[6] * (l[6] - dot), av[7] * (l[7] - dot));
-    }
-  }
+  vlad_contract(QuarterMap{hq, wq}, feat, B, dvc, rn, a, out);
 }
 
-// out[s][k][c0..c0+63] = sum_p a[p][k] xh[p][c] over segment s of `seg_px` quarter-major pixels, in order; `segs`
-// segments per image.  MODE 0 (segs 4, a segment is a quarter): minus A_k centroids[k][c], and A[s][k] = sum_p a[p][k]
-// in fp64 (slice 0 writes it).  MODE 1 (segs 1, the whole image; a = ds): the plain sum, the image's dW.
-// 4 waves as 2 (clusters) x 2 (channels), one 32x32 fp32 accumulator tile each.
+// MODE 0: segs 4, a segment is a quarter of seg_px = Pq pixels.  MODE 1: segs 1, the whole image, seg_px = 4 Pq.
 template <int MODE>
 __global__ __launch_bounds__(256) void rgb_aggregate_kernel(const float* __restrict__ feat,
                                                             const float* __restrict__ rn, const float* __restrict__ a,
                                                             const float* __restrict__ centroids,
                                                             float* __restrict__ out, double* __restrict__ A, int hq,
                                                             int wq, int segs, int seg_px) {
-  constexpr int C = RGB_C;
-  __shared__ __attribute__((aligned(16))) float a_s[32][64];
-  __shared__ __attribute__((aligned(16))) float x_s[32][64];
-  __shared__ float s_sum[64];
-  const int Pq = hq * wq;
-  const int s = blockIdx.x, c0 = blockIdx.y * 64;
-  const int n = s / segs, j0 = (s - n * segs) * seg_px;         // first quarter-major pixel of the segment
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int wm = wave >> 1, wn = wave & 1;
-  const float* fbase = feat + (size_t)n * 4 * Pq * C + c0;
-  const float* abase = a + ((size_t)n * 4 * Pq + j0) * 64;
-  const float* rbase = rn + (size_t)n * 4 * Pq + j0;
-
-  f32x16_t acc;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-  double colsum = 0.0;  // threads 0..63: sum_p a[p][tid]
-
-  const int xp = threadIdx.x >> 3, xc = (threadIdx.x & 7) * 8;
-  float4 pa[2], px0, px1;
-  float psc;
-  auto prefetch = [&](int p0) __attribute__((always_inline)) {
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-      const int idx = threadIdx.x + q * 256;  // float4 index
-      const int pr = idx >> 4, cq = (idx & 15) * 4;
-      pa[q] = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (p0 + pr < seg_px) pa[q] = *reinterpret_cast<const float4*>(abase + (size_t)(p0 + pr) * 64 + cq);
-    }
-    px0 = make_float4(0.f, 0.f, 0.f, 0.f);
-    px1 = px0;
-    psc = 0.f;
-    if (p0 + xp < seg_px) {
-      const int j = j0 + p0 + xp, q = j / Pq;
-      psc = 1.0f / fmaxf(rbase[p0 + xp], RGB_EPS);
-      const float* src = fbase + (size_t)rgb_map_pixel(q, j - q * Pq, hq, wq) * C + xc;
-      px0 = *reinterpret_cast<const float4*>(src);
-      px1 = *reinterpret_cast<const float4*>(src + 4);
-    }
-  };
-  prefetch(0);
-  for (int p0 = 0; p0 < seg_px; p0 += 32) {
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-      const int idx = threadIdx.x + q * 256;
-      *reinterpret_cast<float4*>(&a_s[idx >> 4][(idx & 15) * 4]) = pa[q];
-    }
-    *reinterpret_cast<float4*>(&x_s[xp][xc]) = make_float4(px0.x * psc, px0.y * psc, px0.z * psc, px0.w * psc);
-    *reinterpret_cast<float4*>(&x_s[xp][xc + 4]) = make_float4(px1.x * psc, px1.y * psc, px1.z * psc, px1.w * psc);
-    __syncthreads();
-    if (p0 + 32 < seg_px) prefetch(p0 + 32);
-    if (MODE == 0 && threadIdx.x < 64) {
-#pragma unroll
-      for (int p = 0; p < 32; ++p) colsum += (double)a_s[p][threadIdx.x];
-    }
-#pragma unroll
-    for (int st = 0; st < 16; ++st) {
-      const int p = 2 * st + (lane >> 5);
-      const float av = a_s[p][wm * 32 + (lane & 31)];
-      const float bv = x_s[p][wn * 32 + (lane & 31)];
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc, 0, 0, 0);
-    }
-    __syncthreads();
-  }
-  if (MODE == 0) {
-    if (threadIdx.x < 64) {
-      s_sum[threadIdx.x] = (float)colsum;
-      if (blockIdx.y == 0) A[(size_t)s * 64 + threadIdx.x] = colsum;
-    }
-    __syncthreads();
-  }
-  const int ch = c0 + wn * 32 + (lane & 31);
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int k = wm * 32 + acc_row(r, lane);
-    float v = acc[r];
-    if (MODE == 0) v -= s_sum[k] * centroids[(size_t)k * C + ch];
-    out[((size_t)s * 64 + k) * C + ch] = v;
-  }
+  vlad_aggregate<MODE>(QuarterMap{hq, wq}, feat, rn, a, centroids, out, A, segs, seg_px);
 }
 
 // one wave per (image, cluster): the region rows R_r,k = sum_{q in S_r} V_q,k in fp64 from the four fp32 quarter rows,
 // st[(n 9 + r) K + k] = { |R_r,k| , |U_r,k|^2 , <U_r,k, G_r,k> }
 __global__ __launch_bounds__(256) void rgb_rowstats_kernel(const float* __restrict__ V, const float* __restrict__ G,
                                                            double* __restrict__ st, long rows) {
-  constexpr int C = RGB_C, K = RGB_K;
+  constexpr int C = VLB_C, K = VLB_K;
   const int lane = threadIdx.x & 63;
   const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
@@ -397,9 +119,9 @@ __global__ __launch_bounds__(256) void rgb_rowstats_kernel(const float* __restri
     double ss = 0.0;
 #pragma unroll
     for (int i = 0; i < 8; ++i) ss += rr[i] * rr[i];
-    ss = rgb_wave_sum_f64(ss);
+    ss = wave_sum_f64(ss);
     const double t = sqrt(ss);
-    const double it = 1.0 / fmax(t, (double)RGB_EPS);
+    const double it = 1.0 / fmax(t, (double)VLB_EPS);
     double s2 = 0.0, ug = 0.0;
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
@@ -407,8 +129,8 @@ __global__ __launch_bounds__(256) void rgb_rowstats_kernel(const float* __restri
       s2 += u * u;
       ug += u * gg[i];
     }
-    s2 = rgb_wave_sum_f64(s2);
-    ug = rgb_wave_sum_f64(ug);
+    s2 = wave_sum_f64(s2);
+    ug = wave_sum_f64(ug);
     if (lane == 0) {
       st[3 * rrow] = t;
       st[3 * rrow + 1] = s2;
@@ -428,7 +150,7 @@ __global__ __launch_bounds__(256) void rgb_dv_kernel(float* __restrict__ V, cons
                                                      const double* __restrict__ st, const double* __restrict__ A,
                                                      const float* __restrict__ centroids, float* __restrict__ dvc,
                                                      double* __restrict__ dCp, long rows) {
-  constexpr int C = RGB_C, K = RGB_K;
+  constexpr int C = VLB_C, K = VLB_K;
   const int lane = threadIdx.x & 63;
   const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
@@ -439,14 +161,14 @@ __global__ __launch_bounds__(256) void rgb_dv_kernel(float* __restrict__ V, cons
   for (int r = 0; r < 9; ++r) {
     const long vbase = (n * 9 + r) * K;                             // the region vector's first row
     // |U_r|_F^2 and <U_r, G_r>: lane j holds cluster j's, the same fixed-order sum in every wave of the image
-    const double S2 = rgb_wave_sum_f64(st[3 * (vbase + lane) + 1]);
-    const double UG = rgb_wave_sum_f64(st[3 * (vbase + lane) + 2]);
+    const double S2 = wave_sum_f64(st[3 * (vbase + lane) + 1]);
+    const double UG = wave_sum_f64(st[3 * (vbase + lane) + 2]);
     const double gn = sqrt(S2);
-    const double ig = 1.0 / fmax(gn, (double)RGB_EPS);
-    const double yg = gn < (double)RGB_EPS ? 0.0 : UG * ig;         // <Y_r, G_r>; a clamped g is a constant
+    const double ig = 1.0 / fmax(gn, (double)VLB_EPS);
+    const double yg = gn < (double)VLB_EPS ? 0.0 : UG * ig;         // <Y_r, G_r>; a clamped g is a constant
     const double t = st[3 * (vbase + k)], s2 = st[3 * (vbase + k) + 1], ug = st[3 * (vbase + k) + 2];
-    const double it = 1.0 / fmax(t, (double)RGB_EPS);
-    const double fd = t < (double)RGB_EPS ? 0.0 : (ug - s2 * ig * yg) * ig;   // <U_r,k, dU_r,k>; a clamped t likewise
+    const double it = 1.0 / fmax(t, (double)VLB_EPS);
+    const double fd = t < (double)VLB_EPS ? 0.0 : (ug - s2 * ig * yg) * ig;   // <U_r,k, dU_r,k>; a clamped t likewise
     al[r] = ig * it;
     be[r] = (ig * ig * yg + fd) * it * it;
   }
@@ -504,133 +226,21 @@ __global__ __launch_bounds__(256) void rgb_dv_kernel(float* __restrict__ V, cons
   }
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
-    const double s = rgb_wave_sum_f64(dc[q]);
+    const double s = wave_sum_f64(dc[q]);
     if (lane == 0) dvc[(n * 4 + q) * K + k] = (float)s;
   }
 }
 
-// nvb_dx_kernel on one chunk of one quarter: dxh[p][c] = sum_k a[p][k] dV_q[k][c] + sum_k ds[p][k] w[k][c], then
-// dx_p = (dxh_p - xh_p <xh_p, dxh_p>) / r_p, written to the pixel's place in the map.
 __global__ __launch_bounds__(256) void rgb_dx_kernel(const float* __restrict__ feat, const float* __restrict__ rn,
                                                      const float* __restrict__ a, const float* __restrict__ ds,
                                                      const float* __restrict__ dV, const float* __restrict__ w,
                                                      float* __restrict__ grad_feat, int hq, int wq, int normalize) {
-  constexpr int C = RGB_C;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* const x_s = reinterpret_cast<float*>(smem);             // [32][RGB_XP]
-  float* const ad_s = x_s + 32 * RGB_XP;                          // [32][RGB_AP]: a | ds
-  float* const red_s = ad_s + 32 * RGB_AP;                        // [4 waves][32]
-  float* const inv_s = red_s + 4 * 32;                            // [32]
-  float* const dot_s = inv_s + 32;                                // [32]
-  int* const pix_s = reinterpret_cast<int*>(dot_s + 32);          // [32]
-  const int Pq = hq * wq;
-  const int m = blockIdx.x, p0 = blockIdx.y * 32;
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int l31 = lane & 31, kh = lane >> 5;
-  const size_t jbase = (size_t)m * Pq;
-  dV += (size_t)m * RGB_K * C;
-
-  rgb_chunk_pixels(m & 3, p0, hq, wq, pix_s);
-  if (threadIdx.x < 32) {
-    const int p = p0 + (int)threadIdx.x;
-    inv_s[threadIdx.x] = p < Pq ? 1.0f / fmaxf(rn[jbase + p], RGB_EPS) : 0.f;
-    // the projection is dropped where the input is not normalised or its norm sits on the clamp
-    dot_s[threadIdx.x] = 0.f;
-  }
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {                                   // 32 x 128 floats = 1024 float4
-    const int idx = (int)threadIdx.x + 256 * q;
-    const int px = idx >> 5, k4 = (idx & 31) * 4;                 // k4 < 64: a, else ds
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (p0 + px < Pq) {
-      const float* src = (k4 < 64 ? a : ds) + (jbase + p0 + px) * RGB_K + (k4 & 63);
-      v = *reinterpret_cast<const float4*>(src);
-    }
-    float* d = ad_s + px * RGB_AP + k4;
-    d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
-  }
-  __syncthreads();
-  rgb_load_chunk(feat + (size_t)(m >> 2) * 4 * Pq * C, pix_s, x_s);
-  __syncthreads();
-
-  f32x16_t acc[4];
-#pragma unroll
-  for (int ct = 0; ct < 4; ++ct)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[ct][r] = 0.f;
-  const float* arow = ad_s + l31 * RGB_AP + kh;
-  const int cb = 128 * wave + l31;
-#pragma unroll 1
-  for (int half = 0; half < 2; ++half) {
-    const float* Bm = (half == 0 ? dV : w) + (size_t)kh * C + cb;
-    const float* ar = arow + 64 * half;
-#pragma unroll 4
-    for (int s = 0; s < 32; ++s) {
-      const float av = ar[2 * s];
-      const float* br = Bm + (size_t)(2 * s) * C;
-#pragma unroll
-      for (int ct = 0; ct < 4; ++ct)
-        acc[ct] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, br[32 * ct], acc[ct], 0, 0, 0);
-    }
-  }
-  if (normalize) {
-    // <x_p, dxh_p>: this wave's 128 channels, then the four waves in wave order
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int px = acc_row(r, lane);
-      float v = 0.f;
-#pragma unroll
-      for (int ct = 0; ct < 4; ++ct) v = fmaf(acc[ct][r], x_s[px * RGB_XP + cb + 32 * ct], v);
-      v += __shfl_xor(v, 16, 64);
-      v += __shfl_xor(v, 8, 64);
-      v += __shfl_xor(v, 4, 64);
-      v += __shfl_xor(v, 2, 64);
-      v += __shfl_xor(v, 1, 64);
-      if (l31 == 0) red_s[wave * 32 + px] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < 32) {
-      const int p = p0 + (int)threadIdx.x;
-      const float iv = inv_s[threadIdx.x];
-      const bool clamped = p < Pq ? rn[jbase + p] < RGB_EPS : true;
-      const float d = ((red_s[threadIdx.x] + red_s[32 + threadIdx.x]) + red_s[64 + threadIdx.x]) + red_s[96 + threadIdx.x];
-      dot_s[threadIdx.x] = clamped ? 0.f : d * iv * iv;         // <xh_p, dxh_p> / r_p: it multiplies x_p below
-    }
-    __syncthreads();
-  }
-  float* gimg = grad_feat + (size_t)(m >> 2) * 4 * Pq * C;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int px = acc_row(r, lane);
-    const int mp = pix_s[px];
-    if (mp >= 0) {
-      const float iv = inv_s[px], d = dot_s[px];
-#pragma unroll
-      for (int ct = 0; ct < 4; ++ct) {
-        const int ch = cb + 32 * ct;
-        gimg[(size_t)mp * C + ch] = (acc[ct][r] - x_s[px * RGB_XP + ch] * d) * iv;
-      }
-    }
-  }
+  vlad_dx(QuarterMap{hq, wq}, feat, rn, a, ds, dV, w, grad_feat, normalize);
 }
 
-// dW = sum_n dWp[n] (fp32), dC = sum_n dCp[n] (fp64, rounded once), both in image order; either output may be null
 __global__ __launch_bounds__(256) void rgb_reduce_kernel(const float* __restrict__ dWp, const double* __restrict__ dCp,
                                                          float* __restrict__ dW, float* __restrict__ dC, int N) {
-  constexpr int KC = RGB_K * RGB_C;
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= KC) return;
-  if (dW) {
-    float s = 0.f;
-    for (int n = 0; n < N; ++n) s += dWp[(size_t)n * KC + i];
-    dW[i] = s;
-  }
-  if (dC) {
-    double s = 0.0;
-    for (int n = 0; n < N; ++n) s += dCp[(size_t)n * KC + i];
-    dC[i] = (float)s;
-  }
+  vlad_reduce(dWp, dCp, dW, dC, N);
 }
 
 // The scores' backward: workgroup (float4 block of L, image i of the tuple, tuple t); a thread owns one float4 of
@@ -686,32 +296,16 @@ using namespace oibl;
 
 extern "C" {
 
-// workspace, P = h w, M = 4 N quarters: r [N][P] | a [N][P][64] (quarter-major) | V_q -> dV_q [M][K][C] |
-//            stats [N][9][K][3] fp64 | A [M][K] fp64 | dvc [M][K] | dW of every image [N][K][C] |
-//            dC of every image [N][K][C] fp64 | ds [N][P][64] (only with grad_feat: without it ds overwrites a)
-static size_t rgb_off_a(size_t N, size_t P) { return align_up(N * P * sizeof(float), 256); }
-static size_t rgb_off_v(size_t N, size_t P) { return rgb_off_a(N, P) + align_up(N * P * 64 * sizeof(float), 256); }
-static size_t rgb_off_st(size_t N, size_t P) {
-  return rgb_off_v(N, P) + align_up(4 * N * RGB_K * RGB_C * sizeof(float), 256);
-}
-static size_t rgb_off_A(size_t N, size_t P) { return rgb_off_st(N, P) + align_up(N * 9 * RGB_K * 3 * sizeof(double), 256); }
-static size_t rgb_off_dvc(size_t N, size_t P) { return rgb_off_A(N, P) + align_up(4 * N * RGB_K * sizeof(double), 256); }
-static size_t rgb_off_dwp(size_t N, size_t P) { return rgb_off_dvc(N, P) + align_up(4 * N * RGB_K * sizeof(float), 256); }
-static size_t rgb_off_dcp(size_t N, size_t P) {
-  return rgb_off_dwp(N, P) + align_up(N * RGB_K * RGB_C * sizeof(float), 256);
-}
-static size_t rgb_off_ds(size_t N, size_t P) {
-  return rgb_off_dcp(N, P) + align_up(N * RGB_K * RGB_C * sizeof(double), 256);
-}
+// workspace: vlad_backward_layout with P = h w, four units (the quarters) and nine normalised vectors per image
 static bool rgb_shape_ok(int N, int h, int w, int K, int C) {
-  return N > 0 && N <= 65535 && h >= 2 && w >= 2 && !(h & 1) && !(w & 1) && K == RGB_K && C == RGB_C &&
+  return N > 0 && N <= 65535 && h >= 2 && w >= 2 && !(h & 1) && !(w & 1) && K == VLB_K && C == VLB_C &&
          (long)h * w <= (1L << 22);            // chunks per quarter are a grid's y; N h w stays far below 2^31 rows
 }
 
 size_t oibl_region_backward_workspace_bytes(int N, int h, int w, int K, int C, int want_grad_feat) {
   if (!rgb_shape_ok(N, h, w, K, C)) return 0;
   const size_t P = (size_t)h * w;
-  return rgb_off_ds(N, P) + (want_grad_feat ? align_up((size_t)N * P * 64 * sizeof(float), 256) : 0);
+  return vlad_backward_layout(N, P, 4, 9, want_grad_feat).total;
 }
 
 int oibl_region_vlad_backward(const void* feat, int N, int h, int w, int K, int C, int precision,
@@ -722,7 +316,7 @@ int oibl_region_vlad_backward(const void* feat, int N, int h, int w, int K, int 
   OIBL_REQUIRE(grad_assign_w || grad_centroids || grad_feat, "region_vlad_backward: no output requested");
   OIBL_REQUIRE(precision == OIBL_F32, "region_vlad_backward: the feature map must be fp32 (OIBL_F32), got precision %d",
                precision);
-  OIBL_REQUIRE(K == RGB_K && C == RGB_C,
+  OIBL_REQUIRE(K == VLB_K && C == VLB_C,
                "region_vlad_backward: kernels are built for num_clusters = 64, dim = 512 (got %d, %d)", K, C);
   OIBL_REQUIRE(N > 0 && h > 0 && w > 0, "region_vlad_backward: bad shape N=%d h=%d w=%d", N, h, w);
   OIBL_REQUIRE(!(h & 1) && !(w & 1), "region_vlad_backward: the map is %d x %d, both sides must be even to cut quarters",
@@ -746,15 +340,16 @@ int oibl_region_vlad_backward(const void* feat, int N, int h, int w, int K, int 
   const float* x = (const float*)feat;
   const int hq = h / 2, wq = w / 2, Pq = hq * wq;
   const size_t P = (size_t)h * w;
+  const VladBackwardLayout lay = vlad_backward_layout(N, P, 4, 9, grad_feat != nullptr);
   float* rn = (float*)wsb;
-  float* a = (float*)(wsb + rgb_off_a(N, P));
-  float* V = (float*)(wsb + rgb_off_v(N, P));
-  double* stats = (double*)(wsb + rgb_off_st(N, P));
-  double* A = (double*)(wsb + rgb_off_A(N, P));
-  float* dvc = (float*)(wsb + rgb_off_dvc(N, P));
-  float* dWp = (float*)(wsb + rgb_off_dwp(N, P));
-  double* dCp = grad_centroids ? (double*)(wsb + rgb_off_dcp(N, P)) : nullptr;
-  float* ds = grad_feat ? (float*)(wsb + rgb_off_ds(N, P)) : a;
+  float* a = (float*)(wsb + lay.a);
+  float* V = (float*)(wsb + lay.v);
+  double* stats = (double*)(wsb + lay.stats);
+  double* A = (double*)(wsb + lay.A);
+  float* dvc = (float*)(wsb + lay.dvc);
+  float* dWp = (float*)(wsb + lay.dwp);
+  double* dCp = grad_centroids ? (double*)(wsb + lay.dcp) : nullptr;
+  float* ds = grad_feat ? (float*)(wsb + lay.ds) : a;
   const dim3 pgrid((unsigned)(4 * N), (unsigned)((Pq + 31) / 32));
   const long vrows = (long)N * K;
   const unsigned rgrid = (unsigned)((vrows + 3) / 4);
@@ -790,7 +385,7 @@ int oibl_region_vlad_backward(const void* feat, int N, int h, int w, int K, int 
     OIBL_LAUNCH_CHECK();
   }
   if (grad_assign_w || grad_centroids) {
-    hipLaunchKernelGGL(rgb_reduce_kernel, dim3(RGB_K * RGB_C / 256), dim3(256), 0, st, (const float*)dWp,
+    hipLaunchKernelGGL(rgb_reduce_kernel, dim3(VLB_K * VLB_C / 256), dim3(256), 0, st, (const float*)dWp,
                        (const double*)dCp, grad_assign_w, grad_centroids, N);
     OIBL_LAUNCH_CHECK();
   }
