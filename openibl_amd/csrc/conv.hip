@@ -490,13 +490,6 @@ OIBL_HOOK(int, g_ring_ablate, 0);                     // test hook: see RingPara
 
 // ring-schedule kernel (conv_ring.h): bf16, Cin % 64 == 0; WM = 2: 256 x 256 tile (Cout % 256 == 0),
 // WM = 4: 512 x 128 tile (Cout % 128 == 0)
-// BAR1: the one-barrier-per-phase schedule (ring_core.h).  g_ring_bar1 (test hook): 0 = two barriers per
-// phase (rounds 1-3), 1 = one (the default).  Measured, bit-identical and race-free both times: with the
-// stagger group tested at run time inside the loop 3-8 % SLOWER (profiles/r04_a_bar1_ab.txt); with one kernel
-// body per group 1-4 % faster per layer, 11 % on conv2_1 — f16mx ring + halo layers 7.47 -> 7.25 ms, bf16
-// 4.26 -> 4.19, bf16x3 11.04 -> 10.90 (profiles/r04_b_bar1_ab.txt).
-OIBL_HOOK(int, g_ring_bar1, 1);
-OIBL_HOOK(int, g_ring_stagger, 0);   // experiment: phase groups of the first round (conv_ring.h, RingParams::stagger)
 // a launch over a row sub-range and / or a K split of the layer (conv_ring.h, RingParams; f16mx split-K)
 struct RingSub {
   int tiles_m;       // M tiles of this launch, starting at GEMM row m_base
@@ -507,7 +500,7 @@ struct RingSub {
   long out_rows;
   size_t part_stride;
 };
-template <int WM, bool POOL, bool ODD, int P = RING_BF16, bool OUTMX = (P >= RING_MX), bool BAR1 = false>
+template <int WM, bool POOL, bool ODD, int P = RING_BF16, bool OUTMX = (P >= RING_MX)>
 static int launch_conv_ring_impl(const ConvParams& p, hipStream_t st, const RingSub* sub = nullptr) {
   using G = RingGeo<WM>;
   constexpr bool X3 = P != RING_BF16;  // 4-byte elements
@@ -561,9 +554,9 @@ static int launch_conv_ring_impl(const ConvParams& p, hipStream_t st, const Ring
   q.range_flag = p.range_flag;
   q.bias_mul = p.bias_mul;
   q.out_mul = (sub && sub->parts) ? 1.f : p.out_mul;   // (split-K partials are raw sums: the reduction scales)
-  q.stagger = g_ring_stagger;
+  q.stagger = 0;   // (unread: conv_ring.h)
   constexpr int lds = ring_lds_bytes<WM, POOL, P, OUTMX>();
-  auto kern = conv3x3_ring_kernel<WM, POOL, ODD, P, OUTMX, BAR1>;
+  auto kern = conv3x3_ring_kernel<WM, POOL, ODD, P, OUTMX>;
   OIBL_SET_MAX_LDS(kern, lds);
   hipLaunchKernelGGL(kern, dim3((unsigned)grid, parts), dim3(512), lds, st, q);
   OIBL_LAUNCH_CHECK();
@@ -575,12 +568,7 @@ static int launch_conv_ring(const ConvParams& p, hipStream_t st, const RingSub* 
   // an odd number of K-tiles happens only for Cin = 64 in bf16 (the 4-byte element types have twice
   // the K-tiles), which only the 512 x 128 variant serves
   if constexpr (WM == 4 && P == RING_BF16) {
-    if ((9 * (p.cin / 64)) & 1)
-      return g_ring_bar1 ? launch_conv_ring_impl<WM, POOL, true, P, false, true>(p, st)
-                         : launch_conv_ring_impl<WM, POOL, true>(p, st);
-  }
-  if constexpr (P == RING_BF16 || P == RING_X3 || P == RING_MX_EARLY || P == RING_MX) {
-    if (g_ring_bar1) return launch_conv_ring_impl<WM, POOL, false, P, (P >= RING_MX), true>(p, st, sub);
+    if ((9 * (p.cin / 64)) & 1) return launch_conv_ring_impl<WM, POOL, true>(p, st);
   }
   return launch_conv_ring_impl<WM, POOL, false, P>(p, st, sub);
 }
@@ -700,7 +688,6 @@ static void halo_patch(int Hn, int Wn, int* PH, int* PW) {
   *PW = bw;
 }
 
-OIBL_HOOK(int, g_halo_var, 0);  // experiment: 3 = the waits that count the halo instructions (rarely wrong: conv_halo.h)
 // what the two halo launchers fill the same way; bn: output channels of the kernel's tile
 template <bool POOL>
 static int halo_params(const ConvParams& p, int bn, const char* name, HaloParams& q) {
@@ -742,19 +729,9 @@ static int launch_conv_halo(const ConvParams& p, hipStream_t st) {
   if (const int rc = halo_params<POOL>(p, RingGeo<2>::BN, "halo", q)) return rc;
   q.raster = g_ring_raster;
   const dim3 grid((unsigned)(q.tiles_m * q.tiles_n));
-  if (g_halo_var == 3) {
-    auto kern = conv3x3_halo_kernel<POOL, RING_MX_EARLY, 3>;
-    OIBL_SET_MAX_LDS(kern, HALO_LDS);
-    hipLaunchKernelGGL(kern, grid, dim3(512), HALO_LDS, st, q);
-  } else if (g_ring_bar1) {
-    auto kern = conv3x3_halo_kernel<POOL, RING_MX_EARLY, 0, true>;
-    OIBL_SET_MAX_LDS(kern, HALO_LDS);
-    hipLaunchKernelGGL(kern, grid, dim3(512), HALO_LDS, st, q);
-  } else {
-    auto kern = conv3x3_halo_kernel<POOL, RING_MX_EARLY>;
-    OIBL_SET_MAX_LDS(kern, HALO_LDS);
-    hipLaunchKernelGGL(kern, grid, dim3(512), HALO_LDS, st, q);
-  }
+  auto kern = conv3x3_halo_kernel<POOL, RING_MX>;
+  OIBL_SET_MAX_LDS(kern, HALO_LDS);
+  hipLaunchKernelGGL(kern, grid, dim3(512), HALO_LDS, st, q);
   OIBL_LAUNCH_CHECK();
   return OIBL_OK;
 }
@@ -796,10 +773,9 @@ struct MxSplitPlan {
   long rows_part;   // GEMM rows of the split part
 };
 OIBL_HOOK(int, g_mx_splitk, 1);   // test hook: 0 = never split; 2 = split, reduced by conv_mx_splitk_reduce_kernel
-OIBL_HOOK(int, g_mx_variant, 0);  // test hook: kernel choice of the f16mx layers (launch_conv_mx)
+OIBL_HOOK(int, g_mx_variant, 0);  // test hook: kernel choice of the f16mx layers (launch_conv_mx): 0, 1 or 3
 // the 128-output-channel layers run on conv_halo4.h (256-pixel tiles, two workgroups per CU): no ring rounds to balance
 static bool mx_halo4_layer(int cin, int cout) {
-  if (g_mx_variant == 13) return cout % 128 == 0 && cin % 64 == 0;   // experiment: every layer on conv_halo4.h
   return (g_mx_variant == 0 || g_mx_variant == 3) && cout == 128 && cin % 64 == 0;
 }
 static MxSplitPlan mx_split_plan(long m_plain, int cin, int cout, int pool, int korder, int wm) {
@@ -1012,16 +988,15 @@ __global__ __launch_bounds__(256) void conv_mx_splitk_reduce8_kernel(
 // f16mx: ring kernels (Cin % 64 == 0, Cout % 128 == 0 — every layer of the backbone behind the stem).
 // g_mx_variant (test hook): 0 = that; 3 = the halo kernel (conv_halo.h) for the 256-channel-tile layers —
 // 0.58x the LDS-DMA bytes, +5 % on conv3_x, -5 % on conv4_x / conv5_x since the ring's K cursor left its
-// LOAD segments (profiles/r03_*): kept as the tested alternative; 2 = ring kernels with the LDS-DMA issue
-// inside COMPUTE (RING_MX); 4..8 = timing experiments (wrong results) / stamps.
+// LOAD segments (profiles/r03_*): kept as the tested alternative; 1 = ring kernels only.
 static int launch_conv_mx_split(const ConvParams& p, int pool, const MxSplitPlan& pl, hipStream_t st) {
   // 1. the full rounds, unsplit, straight into the output (never pooled: see mx_split_plan)
   int rc;
   if (pl.tm_main) {
     RingSub main = {};
     main.tiles_m = pl.tm_main;
-    rc = pl.wm == 2 ? launch_conv_ring<2, false, RING_MX_EARLY>(p, st, &main)
-                    : launch_conv_ring<4, false, RING_MX_EARLY>(p, st, &main);
+    rc = pl.wm == 2 ? launch_conv_ring<2, false, RING_MX>(p, st, &main)
+                    : launch_conv_ring<4, false, RING_MX>(p, st, &main);
     if (rc) return rc;
   }
   // 2. the remainder tiles, s parts each, plain pixel order, raw fp32 accumulators
@@ -1038,8 +1013,8 @@ static int launch_conv_mx_split(const ConvParams& p, int pool, const MxSplitPlan
   rem.out = p.partial;
   rem.out_rows = pl.rows_part;
   rem.part_stride = (size_t)pl.rows_part * p.cout * sizeof(float);
-  rc = pl.wm == 2 ? launch_conv_ring<2, false, RING_MX_EARLY>(q, st, &rem)
-                  : launch_conv_ring<4, false, RING_MX_EARLY>(q, st, &rem);
+  rc = pl.wm == 2 ? launch_conv_ring<2, false, RING_MX>(q, st, &rem)
+                  : launch_conv_ring<4, false, RING_MX>(q, st, &rem);
   if (rc) return rc;
   // 3. bias + parts in order, ReLU, pool, pack
   const long out_row0 = pool ? 0 : pl.m_base;
@@ -1087,26 +1062,12 @@ static int launch_conv_mx(const ConvParams& p, int pool, hipStream_t st) {
   if (halo_ok && (g_mx_variant == 3 || (g_mx_variant == 0 && p.cout == 256)))
     return pool ? launch_conv_halo<true>(p, st) : launch_conv_halo<false>(p, st);
   // the 4-wave halo kernel (conv_halo4.h) for the 128-output-channel layers (rv == 4: conv2_1 / conv2_2): a third
-  // of the ring's L2 -> LDS bytes per K-tile.  Hook: 1 = ring kernels; 13 = EVERY layer on it (experiment: conv3_x
-  // ties with the 8-wave halo kernel, conv4_x / conv5_x lose 12-16 %, profiles/r05_*_timing.txt).
-  if ((rv == 4 || (g_mx_variant == 13 && rv == 2)) && mx_halo4_layer(p.cin, p.cout))
+  // of the ring's L2 -> LDS bytes per K-tile.  Hook: 1 = ring kernels.  (On every layer it was an experiment: conv3_x
+  // ties with the 8-wave halo kernel, conv4_x / conv5_x lose 12-16 %, profiles/r05_*_timing.txt.)
+  if (rv == 4 && mx_halo4_layer(p.cin, p.cout))
     return pool ? launch_conv_halo4<true>(p, st) : launch_conv_halo4<false>(p, st);
-  if (g_mx_variant == 2) {
-    if (rv == 2) return pool ? launch_conv_ring<2, true, RING_MX>(p, st) : launch_conv_ring<2, false, RING_MX>(p, st);
-    if (rv == 4) return pool ? launch_conv_ring<4, true, RING_MX>(p, st) : launch_conv_ring<4, false, RING_MX>(p, st);
-  }
-  if (g_mx_variant == 8 && rv == 2 && !pool) return launch_conv_ring<2, false, RING_MX_PROF>(p, st);
-  if (g_mx_variant == 8 && rv == 4 && !pool) return launch_conv_ring<4, false, RING_MX_PROF>(p, st);
-  if (g_mx_variant >= 4 && g_mx_variant <= 7 && rv == 2 && !pool) {   // timing experiments (wrong results)
-    switch (g_mx_variant) {
-      case 4: return launch_conv_ring<2, false, RING_MX_NOMFMA>(p, st);
-      case 5: return launch_conv_ring<2, false, RING_MX_NODMA>(p, st);
-      case 6: return launch_conv_ring<2, false, RING_MX_NOREAD>(p, st);
-      default: return launch_conv_ring<2, false, RING_MX_NOBAR>(p, st);
-    }
-  }
-  if (rv == 2) return pool ? launch_conv_ring<2, true, RING_MX_EARLY>(p, st) : launch_conv_ring<2, false, RING_MX_EARLY>(p, st);
-  if (rv == 4) return pool ? launch_conv_ring<4, true, RING_MX_EARLY>(p, st) : launch_conv_ring<4, false, RING_MX_EARLY>(p, st);
+  if (rv == 2) return pool ? launch_conv_ring<2, true, RING_MX>(p, st) : launch_conv_ring<2, false, RING_MX>(p, st);
+  if (rv == 4) return pool ? launch_conv_ring<4, true, RING_MX>(p, st) : launch_conv_ring<4, false, RING_MX>(p, st);
   set_error("conv3x3 (f16mx): unsupported layer cin=%d cout=%d at N=%d H=%d W=%d (needs Cin %% 64 == 0, "
             "Cout %% 128 == 0 and an input below 3.5 GB)", p.cin, p.cout, p.N, p.H, p.W);
   return OIBL_E_UNSUPPORTED;
@@ -1269,9 +1230,8 @@ int oibl_debug_set_conv_splitk(int on) {
   return OIBL_OK;
 }
 
-int oibl_debug_set_mx_variant(int v) {
-  g_halo_var = v >= 16 ? v - 16 : 0;   // 19: halo kernel with the unsafe waits (experiment)
-  if (v >= 16) v = 3;
+int oibl_debug_set_mx_variant(int v) {   // 0 = auto, 1 = ring kernels only, 3 = halo kernel wherever legal
+  OIBL_REQUIRE(v == 0 || v == 1 || v == 3, "oibl_debug_set_mx_variant: %d is not one of 0, 1, 3", v);
   g_mx_variant = v;
   return OIBL_OK;
 }
@@ -1283,16 +1243,6 @@ int oibl_debug_set_conv_korder(int mode) {
 
 int oibl_debug_set_mx_splitk(int on) {
   g_mx_splitk = on == 2 ? 2 : (on ? 1 : 0);
-  return OIBL_OK;
-}
-
-int oibl_debug_set_ring_stagger(int sleeps) {
-  g_ring_stagger = sleeps < 0 ? 0 : sleeps;
-  return OIBL_OK;
-}
-
-int oibl_debug_set_ring_bar1(int on) {
-  g_ring_bar1 = on ? 1 : 0;
   return OIBL_OK;
 }
 

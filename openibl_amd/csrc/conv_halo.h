@@ -76,7 +76,7 @@ template <int P, bool SWAP, typename Prep>
 __device__ static inline void halo_phase_mma(f32x16_t& acc0, f32x16_t& acc1, const bf16x8_t (&fa)[2][4],
                                              const bf16x8_t (&fb)[4], Prep&& prep, bool prio2 = false) {
   __builtin_amdgcn_sched_barrier(0);
-  if (prio2) __builtin_amdgcn_s_setprio(2);   // (BAR1, group 0, a compile-time constant at every call: ring_core.h)
+  if (prio2) __builtin_amdgcn_s_setprio(2);   // (stagger group 0, a compile-time constant at every call: ring_core.h)
   else __builtin_amdgcn_s_setprio(1);
   if constexpr (P >= RING_MX) {
     typedef __attribute__((ext_vector_type(4))) int i4;
@@ -124,18 +124,16 @@ __device__ static inline void halo_phase_mma(f32x16_t& acc0, f32x16_t& acc1, con
   __builtin_amdgcn_sched_barrier(0);
 }
 
-// VAR (experiments kept for tests/gpu_halo_determinism.py): 0 = production; 3 = the waits that count the
-// halo instructions as outstanding (vmcnt(6) / vmcnt(5)) with out-of-range dummies: rarely WRONG, see below.
-// BAR1: one barrier per phase and wave (ring_core.h) — the same hazard distances hold here; GROUP as in
+// One barrier per phase and wave (ring_core.h) — the same hazard distances hold here; GROUP as in
 // conv3x3_ring_body (conv_ring.h).
-template <bool POOL, int P, int VAR, bool BAR1, int GROUP>
+template <bool POOL, int P, int GROUP>
 __device__ __forceinline__ void conv3x3_halo_body(const HaloParams& p, char* smem, const int lane, const int wave) {
   using G = RingGeo<2>;
   constexpr bool MX = P >= RING_MX;
   constexpr bool SWAP = !POOL;
   constexpr int NB = G::NB;
   const int wm = wave / G::WN, wn = wave % G::WN;
-  const int group = wave >> 2;
+  static_assert(GROUP == 0 || GROUP == 1, "the caller fixes the stagger group");
   int tm, tn;
   xcd_tile(blockIdx.x, (unsigned)p.tiles_m, (unsigned)p.tiles_n, p.raster, tm, tn);
   const unsigned img = ring_div_u31((unsigned)tm, p.img_mul, p.img_sh);
@@ -174,7 +172,7 @@ __device__ __forceinline__ void conv3x3_halo_body(const HaloParams& p, char* sme
       char* dst = real ? smem + hb * HALO_BYTES + ii * 1024 : sink;
       buf_glds16(rs_in, hvoff[j], (unsigned)(real ? cc : 0) * 128u, dst);
     } else {
-      buf_glds16(rs_in, VAR == 3 ? RG_OOB : (unsigned)(lane * 16), 0u, sink);   // in range: see the waits
+      buf_glds16(rs_in, (unsigned)(lane * 16), 0u, sink);   // in range: see the waits
     }
   };
 
@@ -198,7 +196,7 @@ __device__ __forceinline__ void conv3x3_halo_body(const HaloParams& p, char* sme
       lb.stage(h, st_b + buf * HALO_B_TILE + h * G::B_UNIT);
     } else {
 #pragma unroll
-      for (int i = 0; i < NB; ++i) buf_glds16(lb.rsrc, VAR == 3 ? RG_OOB : (unsigned)(lane * 16), 0u, sink);
+      for (int i = 0; i < NB; ++i) buf_glds16(lb.rsrc, (unsigned)(lane * 16), 0u, sink);
     }
   };
 
@@ -288,15 +286,11 @@ __device__ __forceinline__ void conv3x3_halo_body(const HaloParams& p, char* sme
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
   };
-  // BAR1: the stagger group is a compile-time constant of one of two copies of the K loop (ring_core.h, GROUP)
+  // the barrier in front of (g = 0) / behind (g = 1) a COMPUTE segment: only group g crosses it (ring_core.h)
   auto bar_g = [&](auto grp_c, int g) __attribute__((always_inline)) {
-    if constexpr (BAR1) {
-      __builtin_amdgcn_sched_barrier(0);
-      if (decltype(grp_c)::value == g) __builtin_amdgcn_s_barrier();
-      __builtin_amdgcn_sched_barrier(0);
-    } else {
-      bar();
-    }
+    __builtin_amdgcn_sched_barrier(0);
+    if (decltype(grp_c)::value == g) __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_sched_barrier(0);
   };
 
   // accumulators start at the bias (conv_ring.h)
@@ -348,14 +342,11 @@ __device__ __forceinline__ void conv3x3_halo_body(const HaloParams& p, char* sme
   bar();
   read_b(0, 0, fbx);
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  if constexpr (!BAR1) {
-    if (group == 1) bar();  // group 1 runs one barrier behind group 0
-  }
 
   // one K-tile = tap `TAP` of channel chunk cc (halo buffer hb); PAR = parity of the K-tile (weight buffer,
   // register set of B0); kt = its index
   auto ktile = [&](auto grp_c, auto par_c, auto tap_c, int hb, int cc, int kt) __attribute__((always_inline)) {
-    constexpr bool prio2 = BAR1 && decltype(grp_c)::value == 0;
+    constexpr bool prio2 = decltype(grp_c)::value == 0;
     constexpr int PAR = decltype(par_c)::value;
     constexpr int TAP = decltype(tap_c)::value;
     bf16x8_t(&b0)[4] = PAR ? fby : fbx;
@@ -368,10 +359,10 @@ __device__ __forceinline__ void conv3x3_halo_body(const HaloParams& p, char* sme
     // younger instructions here, B0(t+1) in P2 has NB + 1 + NB.  But an LDS-DMA instruction whose 64 lanes are
     // ALL out of range — the halo slots of a border tile's outside rows — was seen to retire ahead of older
     // in-range loads: with vmcnt(6) / vmcnt(5) one tile in ~100 launches came out wrong, always a top- or
-    // bottom-row tile, more often with another stream loading the memory system (tests/gpu_halo_determinism.py:
-    // 8 of 270 launches; 0 of 270 with the waits below).  So the halo instructions are not counted — the
+    // bottom-row tile, more often with another stream loading the memory system (8 of 270 launches; 0 of 270
+    // with the waits below).  So the halo instructions are not counted — the
     // waits allow only the 2 x NB younger WEIGHT instructions in flight — and every dummy is an in-range load.
-    wait_vmcnt<(VAR == 3 ? 1 + 2 * NB + 1 : 2 * NB)>();
+    wait_vmcnt<2 * NB>();
     bar_g(grp_c, 0);
     halo_phase_mma<P, SWAP>(acc[0][0], acc[1][0], fa, b0, [&] { lb.begin_tile(); }, prio2);  // (cursor -> K-tile
     bar_g(grp_c, 1);                          // t+2; unconditional: advanced under a branch it ends up in a VGPR)
@@ -383,7 +374,7 @@ __device__ __forceinline__ void conv3x3_halo_body(const HaloParams& p, char* sme
     bar_g(grp_c, 1);
     // P2: A1 x B1
     read_a(hb, I1{}, tap_c);
-    wait_vmcnt<(VAR == 3 ? 2 * NB + 1 : 2 * NB)>();
+    wait_vmcnt<2 * NB>();
     bar_g(grp_c, 0);
     halo_phase_mma<P, SWAP>(acc[2][1], acc[3][1], fa, b1, [] {}, prio2);
     bar_g(grp_c, 1);
@@ -419,11 +410,8 @@ __device__ __forceinline__ void conv3x3_halo_body(const HaloParams& p, char* sme
       ktile(grp_c, I1{}, HALO_IC(8), 1, cc + 1, kt + 17);
     }
   };
-  run(std::integral_constant<int, (GROUP == 1 ? 1 : 0)>{});
+  run(std::integral_constant<int, GROUP>{});
 #undef HALO_IC
-  if constexpr (!BAR1) {
-    if (group == 0) bar();
-  }
   wait_vmcnt<0>();  // (sink writes of the last dummies)
   __syncthreads();
   if (p.out_mul != 1.f) {   // (uniform; the layer handing the fp32 map to the head: conv_ring.h)
@@ -536,17 +524,13 @@ __device__ __forceinline__ void conv3x3_halo_body(const HaloParams& p, char* sme
   }
 }
 
-template <bool POOL, int P, int VAR = 0, bool BAR1 = false>
+template <bool POOL, int P>
 __global__ __launch_bounds__(512) void conv3x3_halo_kernel(HaloParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  if constexpr (BAR1) {
-    if ((wave >> 2) == 0) conv3x3_halo_body<POOL, P, VAR, true, 0>(p, smem, lane, wave);
-    else conv3x3_halo_body<POOL, P, VAR, true, 1>(p, smem, lane, wave);
-  } else {
-    conv3x3_halo_body<POOL, P, VAR, false, -1>(p, smem, lane, wave);
-  }
+  if ((wave >> 2) == 0) conv3x3_halo_body<POOL, P, 0>(p, smem, lane, wave);
+  else conv3x3_halo_body<POOL, P, 1>(p, smem, lane, wave);
 }
 
 }  // namespace oibl

@@ -57,7 +57,7 @@ static_assert(2 * H4_LDS <= 160 * 1024, "two workgroups per CU");
 
 template <bool POOL>
 __global__ __launch_bounds__(H4_THREADS, 2) void conv3x3_halo4_kernel(HaloParams p) {
-  constexpr int P = RING_MX_EARLY;
+  constexpr int P = RING_MX;
   constexpr bool SWAP = !POOL;
   constexpr int NB = H4_NB;
   extern __shared__ __attribute__((aligned(16))) char smem[];

@@ -59,10 +59,9 @@ struct RingParams {
   // row (m - m_base); conv_mx_splitk_reduce_kernel adds bias and partials in a fixed order.
   int m_base, nsteps_part, k_outer_step;
   size_t part_stride;
-  // Experiment (test hook, 0 = off): the workgroups of the FIRST round start (blockIdx & 3) * stagger sleeps of
-  // 8128 cycles late.  All workgroups of a layer run for the same time, so the rounds stay in phase across the
-  // chip: every CU loads, then every CU stores its tile (conv2_1: 64 MB of lines per round inside ~9 us); four
-  // phase groups spread those bursts over the round.
+  // Unread, always 0: the start-up stagger experiment that read it has left the tree
+  // (profiles/r04_n_stagger_ab.txt: 0.3 % of the step).  The field keeps the kernel-argument layout, and with
+  // it the kernels' text, as measured.
   int stagger;
 };
 
@@ -222,11 +221,11 @@ struct ConvRingBLoader {
 // OUTMX: the output is written as f16mx lines (always with f16mx operands; the parameter exists because the
 // epilogue only depends on it: bf16x3 operands with f16mx output compile too — round 3 ran conv2_1 that way
 // until the stem itself became f16mx).
-// The kernel's body.  GROUP: -1, or (BAR1) the stagger group of the calling wave as a compile-time constant —
-// the kernel then holds one copy of the body per group (ring_core.h, GROUP: two copies of the LOOP that merged
-// again in front of a shared epilogue made the register allocator spill; a lambda around the body put the
-// kernel arguments on the stack).
-template <int WM, bool POOL, bool ODD, int P, bool OUTMX, bool BAR1, int GROUP>
+// The kernel's body.  GROUP: the stagger group of the calling wave as a compile-time constant — the kernel
+// holds one copy of the body per group (ring_core.h, GROUP: two copies of the LOOP that merged again in front
+// of a shared epilogue made the register allocator spill; a lambda around the body put the kernel arguments
+// on the stack).
+template <int WM, bool POOL, bool ODD, int P, bool OUTMX, int GROUP>
 __device__ __forceinline__ void conv3x3_ring_body(const RingParams& p, char* smem, const int lane, const int wave) {
   using G = RingGeo<WM>;
   constexpr int NA = G::NA, NB = G::NB;
@@ -310,8 +309,7 @@ __device__ __forceinline__ void conv3x3_ring_body(const RingParams& p, char* sme
   }
 
   const unsigned long long t_loop = prof ? __builtin_amdgcn_s_memtime() : 0;
-  ring_mainloop<WM, ODD, !POOL, P, BAR1, GROUP>(acc, smem, wave, lane, la, lb, nsteps,
-                                                (P == RING_MX_PROF && blockIdx.x == 0 && p.prof) ? p.prof + 8 : nullptr);
+  ring_mainloop<WM, ODD, !POOL, P, GROUP>(acc, smem, wave, lane, la, lb, nsteps);
   // (the main loop ends on a workgroup barrier: the staging LDS is free for the epilogue)
   if (p.out_mul != 1.f) {   // (uniform; one layer of the f16mx backbone)
 #pragma unroll
@@ -570,23 +568,13 @@ __device__ __forceinline__ void conv3x3_ring_body(const RingParams& p, char* sme
   }
 }
 
-template <int WM, bool POOL, bool ODD, int P = RING_BF16, bool OUTMX = (P >= RING_MX), bool BAR1 = false>
+template <int WM, bool POOL, bool ODD, int P = RING_BF16, bool OUTMX = (P >= RING_MX)>
 __global__ __launch_bounds__(512) void conv3x3_ring_kernel(RingParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-#ifdef OIBL_DEBUG_HOOKS
-  if (p.stagger > 0 && blockIdx.x < 256 && blockIdx.y == 0) {
-    const int n = (int)(blockIdx.x & 3) * p.stagger;
-    for (int i = 0; i < n; ++i) __builtin_amdgcn_s_sleep(127);
-  }
-#endif
-  if constexpr (BAR1) {
-    if ((wave >> 2) == 0) conv3x3_ring_body<WM, POOL, ODD, P, OUTMX, true, 0>(p, smem, lane, wave);
-    else conv3x3_ring_body<WM, POOL, ODD, P, OUTMX, true, 1>(p, smem, lane, wave);
-  } else {
-    conv3x3_ring_body<WM, POOL, ODD, P, OUTMX, false, -1>(p, smem, lane, wave);
-  }
+  if ((wave >> 2) == 0) conv3x3_ring_body<WM, POOL, ODD, P, OUTMX, 0>(p, smem, lane, wave);
+  else conv3x3_ring_body<WM, POOL, ODD, P, OUTMX, 1>(p, smem, lane, wave);
 }
 
 }  // namespace oibl

@@ -228,7 +228,7 @@ struct PairRingParams {
   float thr_slack;
 };
 
-template <bool FILTER, int P = RING_BF16, bool BAR1 = false>
+template <bool FILTER, int P = RING_BF16>
 __global__ __launch_bounds__(512) void pairwise_ring_kernel(PairRingParams p) {
   using G = RingGeo<2>;
   constexpr bool X3 = P != RING_BF16;  // 4-byte operand elements, 32 K per K-tile (bf16x3 and f16mx)
@@ -272,12 +272,9 @@ __global__ __launch_bounds__(512) void pairwise_ring_kernel(PairRingParams p) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
-  if constexpr (BAR1) {   // one copy of the loop per stagger group (ring_core.h)
-    if ((wave >> 2) == 0) ring_mainloop<2, false, false, P, true, 0>(acc, smem, wave, lane, la, lb, d_part >> (X3 ? 5 : 6));
-    else ring_mainloop<2, false, false, P, true, 1>(acc, smem, wave, lane, la, lb, d_part >> (X3 ? 5 : 6));
-  } else {
-    ring_mainloop<2, false, false, P>(acc, smem, wave, lane, la, lb, d_part >> (X3 ? 5 : 6));
-  }
+  // one copy of the loop per stagger group (ring_core.h)
+  if ((wave >> 2) == 0) ring_mainloop<2, false, false, P, 0>(acc, smem, wave, lane, la, lb, d_part >> (X3 ? 5 : 6));
+  else ring_mainloop<2, false, false, P, 1>(acc, smem, wave, lane, la, lb, d_part >> (X3 ? 5 : 6));
 
   // norms (and thresholds) of the tile's rows / columns -> LDS; out-of-range rows/columns are
   // clamped here and masked at the store
@@ -896,22 +893,10 @@ extern "C" {
 OIBL_HOOK(int, g_match_ring, 1);  // test hook: 0 = never, 1 = auto, 2 = whenever legal
 OIBL_HOOK(int, g_match_group, 4);  // test hook: query tiles per ordering group of the ring kernel
 OIBL_HOOK(int, g_match_splitk, 1);  // test hook: 0 = never split the threshold sample's contraction
-// f16mx distances: 1 = LDS-DMA issue in the LOAD segments (as the convolutions; the default since the one-barrier
-// schedule: 7.72-7.76 ms against 7.85-7.93 for 8192 x 81920 x 4096 + top-10, same bits), 0 = inside COMPUTE
-OIBL_HOOK(int, g_match_mx_early, 1);
-OIBL_HOOK(int, g_match_bar1, 1);    // test hook: 0 = two barriers per phase in the ring kernel (ring_core.h, BAR1: 1 = 0-2.5 % faster)
 
 #ifdef OIBL_DEBUG_HOOKS
 int oibl_debug_set_match_splitk(int on) {
   g_match_splitk = on ? 1 : 0;
-  return OIBL_OK;
-}
-int oibl_debug_set_match_bar1(int on) {
-  g_match_bar1 = on ? 1 : 0;
-  return OIBL_OK;
-}
-int oibl_debug_set_match_mx_early(int on) {
-  g_match_mx_early = on ? 1 : 0;
   return OIBL_OK;
 }
 #endif
@@ -982,15 +967,9 @@ static int launch_pairwise_ring(PairRingParams& p, hipStream_t st, int ksplit = 
   const long grid = (long)p.tiles_m * p.tiles_n;
   OIBL_REQUIRE(grid > 0 && grid <= 0x7fffffffL, "pairwise: grid out of range");
   constexpr int lds = RingGeo<2>::MAIN_LDS;
-  if (g_match_bar1) {   // one barrier per phase (ring_core.h, BAR1)
-    auto kern = pairwise_ring_kernel<FILTER, P, true>;
-    OIBL_SET_MAX_LDS(kern, lds);
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid, (unsigned)ksplit), dim3(512), lds, st, p);
-  } else {
-    auto kern = pairwise_ring_kernel<FILTER, P>;
-    OIBL_SET_MAX_LDS(kern, lds);
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid, (unsigned)ksplit), dim3(512), lds, st, p);
-  }
+  auto kern = pairwise_ring_kernel<FILTER, P>;
+  OIBL_SET_MAX_LDS(kern, lds);
+  hipLaunchKernelGGL(kern, dim3((unsigned)grid, (unsigned)ksplit), dim3(512), lds, st, p);
   OIBL_LAUNCH_CHECK();
   return OIBL_OK;
 }
@@ -1072,8 +1051,7 @@ static int pairwise_launch(const void* xo, const void* yo, const float* xn, cons
         q.m = pr;
         q.n = pc;
         q.d = d;
-        const int rc = g_match_mx_early ? launch_pairwise_ring<false, RING_MX_EARLY>(q, st)
-                                        : launch_pairwise_ring<false, RING_MX>(q, st);
+        const int rc = launch_pairwise_ring<false, RING_MX>(q, st);
         if (rc) return rc;
       }
     return OIBL_OK;
@@ -1290,8 +1268,7 @@ static int sqdist_topk_core(const void* xo, const float* xn, int m, const void* 
       q.part_stride = half;
       q.yn_max = (unsigned*)(cnt + m);
     }
-    rc = mx   ? (g_match_mx_early ? launch_pairwise_ring<false, RING_MX_EARLY>(q, st, t.ksplit)
-                                  : launch_pairwise_ring<false, RING_MX>(q, st, t.ksplit))
+    rc = mx   ? launch_pairwise_ring<false, RING_MX>(q, st, t.ksplit)
          : x3 ? launch_pairwise_ring<false, RING_X3>(q, st, t.ksplit)
               : launch_pairwise_ring<false>(q, st, t.ksplit);
     if (rc) return rc;
@@ -1315,8 +1292,7 @@ static int sqdist_topk_core(const void* xo, const float* xn, int m, const void* 
     q.cap = t.cap;
     q.index_base = index_base;
     q.index_stride = 1;
-    rc = mx   ? (g_match_mx_early ? launch_pairwise_ring<true, RING_MX_EARLY>(q, st)
-                                  : launch_pairwise_ring<true, RING_MX>(q, st))
+    rc = mx   ? launch_pairwise_ring<true, RING_MX>(q, st)
          : x3 ? launch_pairwise_ring<true, RING_X3>(q, st)
               : launch_pairwise_ring<true>(q, st);
     if (rc) return rc;
@@ -1495,15 +1471,9 @@ static int launch_pairwise_f16r(F16rParams& p, hipStream_t st, int ksplit = 1) {
   const long grid = (long)p.tiles_m * p.tiles_n;
   OIBL_REQUIRE(grid > 0 && grid <= 0x7fffffffL, "sqdist_topk_f16r: grid out of range");
   constexpr int lds = RingGeo<2>::MAIN_LDS;
-  if (g_match_bar1) {
-    auto kern = pairwise_f16r_kernel<FILTER, true>;
-    OIBL_SET_MAX_LDS(kern, lds);
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid, (unsigned)ksplit), dim3(512), lds, st, p);
-  } else {
-    auto kern = pairwise_f16r_kernel<FILTER, false>;
-    OIBL_SET_MAX_LDS(kern, lds);
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid, (unsigned)ksplit), dim3(512), lds, st, p);
-  }
+  auto kern = pairwise_f16r_kernel<FILTER>;
+  OIBL_SET_MAX_LDS(kern, lds);
+  hipLaunchKernelGGL(kern, dim3((unsigned)grid, (unsigned)ksplit), dim3(512), lds, st, p);
   OIBL_LAUNCH_CHECK();
   return OIBL_OK;
 }

@@ -135,7 +135,7 @@ __global__ __launch_bounds__(256) void f16r_prepare_kernel(const void* __restric
 // The ring distance kernel on fp16 rows (RING_F16: the bf16 stream with v_mfma_f32_32x32x16_f16), tile order and
 // main loop exactly pairwise_ring_kernel's; the epilogue undoes the row scales and, with FILTER, widens every
 // row's threshold by the pair's error bound.
-template <bool FILTER, bool BAR1>
+template <bool FILTER>
 __global__ __launch_bounds__(512) void pairwise_f16r_kernel(F16rParams p) {
   using G = RingGeo<2>;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -175,12 +175,9 @@ __global__ __launch_bounds__(512) void pairwise_f16r_kernel(F16rParams p) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
-  if constexpr (BAR1) {
-    if ((wave >> 2) == 0) ring_mainloop<2, false, false, RING_F16, true, 0>(acc, smem, wave, lane, la, lb, d_part >> 6);
-    else ring_mainloop<2, false, false, RING_F16, true, 1>(acc, smem, wave, lane, la, lb, d_part >> 6);
-  } else {
-    ring_mainloop<2, false, false, RING_F16>(acc, smem, wave, lane, la, lb, d_part >> 6);
-  }
+  // one copy of the loop per stagger group (ring_core.h)
+  if ((wave >> 2) == 0) ring_mainloop<2, false, false, RING_F16, 0>(acc, smem, wave, lane, la, lb, d_part >> 6);
+  else ring_mainloop<2, false, false, RING_F16, 1>(acc, smem, wave, lane, la, lb, d_part >> 6);
 
   float* const xn_s = reinterpret_cast<float*>(smem);   // 256 floats each
   float* const yn_s = xn_s + 256;

@@ -15,31 +15,38 @@
 //   * a K-tile is four PHASES, one per 64 x 32 quadrant of the wave's 128 x 64 accumulator
 //     (8 MFMAs 32x32x16 each).  Every phase is a LOAD segment (fragment ds_reads of the operand
 //     half that changes: 8, 4, 8, 4 reads; the LDS-DMA instructions of one unit; the counted wait)
-//     and a COMPUTE segment (8 MFMAs behind counted lgkmcnt waits), separated by raw s_barriers;
-//   * the two stagger groups (waves 0-3 / 4-7: one wave of each on every SIMD) run ONE BARRIER
-//     APART: while one wave of a SIMD is in its COMPUTE segment the other is in its LOAD segment,
-//     so the matrix pipe of the SIMD always has a wave with operands in registers (s_setprio 1
-//     around the MFMAs lets it win issue arbitration against the loading partner).
-//   * BAR1 (round 4): ONE barrier per phase and wave instead of two.  Every wave runs the same sequence
-//     L(0) C(0) L(1) C(1) ...; group 0 crosses its barrier between L(p) and C(p), group 1 between C(p) and
-//     L(p+1).  Barrier interval n then holds  group 0: C(n-1) L(n)   |   group 1: L(n) C(n)  — the two
-//     COMPUTE segments of a SIMD run back to back on its matrix pipe (group 0 at the higher priority: its
-//     LOAD is still to come), each LOAD segment in the shadow of the partner's COMPUTE, and the barrier
-//     latency + arrival skew is paid once per 2 x COMPUTE instead of once per COMPUTE (with 6 MFMAs =
-//     192 pipe cycles per f16mx phase the two-barrier interval measured 245-277 cycles).  Hazards, with
-//     intervals counted like phases: the fragment reads of phase r are retired inside C(r) (counted
-//     waits in front of the MFMAs that use them, lgkmcnt(0) behind the last one): in interval r (group 1) or at the head of interval r+1 (group 0) — a unit re-staged in
-//     L(q), q >= r+2, is issued in interval >= r+2 by either group: WAR as before.  A wait in L(w) is
-//     followed by barrier w in both groups (directly in group 0, behind C(w) in group 1); the reads of
-//     L(w+1) come after barrier w in both: RAW as before (read >= 1 phase after the retiring wait).
+//     and a COMPUTE segment (8 MFMAs behind counted lgkmcnt waits);
+//   * the two stagger groups (waves 0-3 / 4-7: one wave of each on every SIMD) cross ONE raw s_barrier per
+//     phase and wave.  Every wave runs the same sequence L(0) C(0) L(1) C(1) ...; group 0 crosses its barrier
+//     between L(p) and C(p), group 1 between C(p) and L(p+1).  Barrier interval n then holds
+//         group 0: C(n-1) L(n)   |   group 1: L(n) C(n)
+//     — the two COMPUTE segments of a SIMD run back to back on its matrix pipe (group 0 at s_setprio 2, group 1
+//     at 1: group 0's LOAD is still to come), each LOAD segment in the shadow of the partner's COMPUTE, so the
+//     matrix pipe of the SIMD always has a wave with operands in registers, and the barrier latency + arrival
+//     skew is paid once per 2 x COMPUTE.
+//     Hazards, with intervals counted like phases: the fragment reads of phase r are retired inside C(r)
+//     (counted waits in front of the MFMAs that use them, lgkmcnt(0) behind the last one): in interval r
+//     (group 1) or at the head of interval r+1 (group 0) — a unit re-staged in L(q), q >= r+2, is issued in
+//     interval >= r+2 by either group: WAR.  A wait in L(w) is followed by barrier w in both groups (directly
+//     in group 0, behind C(w) in group 1); the reads of L(w+1) come after barrier w in both: RAW (read >= 1
+//     phase after the retiring wait).
+//   * the LDS-DMA instructions of a phase are issued in its LOAD segment, behind the fragment reads; the
+//     scalar K-cursor advance they need runs one phase earlier, between the MFMAs (ktile, `prep`).
+//
+// Measured and removed (the measurements stay under profiles/): a schedule with TWO barriers per phase, the
+// groups one barrier apart, was 1-4 % slower per layer and 11 % on conv2_1 (r04_a_bar1_ab.txt,
+// r04_b_bar1_ab.txt; 245-277 cycles per two-barrier interval against 192 pipe cycles of an f16mx phase); an
+// f16mx stream that issued its LDS-DMA inside COMPUTE, between the MFMAs ("late issue", operand code 2), lost
+// to the issue order above on every layer and in the distance kernel (r04_e_precbench.txt,
+// r04_f_match_early_ab.txt).
 //
 // Hazard rules (cdna_hip_programming.md, "256^2 8-phase template"), with phases numbered globally:
 //   RAW  a unit is read in phase >= w + 1 where w is the phase whose LOAD segment holds the
-//        vmcnt that retires it (own loads) and whose closing barriers make the other waves' loads
+//        vmcnt that retires it (own loads) and whose barrier makes the other waves' loads
 //        visible;  here w = read - 1 and the wait after the phase's own issues leaves exactly the
 //        5 youngest units outstanding.
-//   WAR  a unit is re-staged in phase >= r + 2 where r is the last phase that reads it (the
-//        lagging group retires those reads after the barrier that ends phase r).
+//   WAR  a unit is re-staged in phase >= r + 2 where r is the last phase that reads it (group 0
+//        retires those reads at the head of barrier interval r + 1).
 // Unit schedule for K-tile t (phases 4t .. 4t+3), reads / (re)stages:
 //   P0: read A0(t)            stage A1(t+1)          P1: read B1(t)       stage B0(t+2)
 //   P2: read A1(t)            stage A0(t+2)          P3: read B0(t+1)     stage B1(t+2)
@@ -74,13 +81,8 @@ constexpr int RING_F16 = -1;  // fp16 rows: the bf16 stream with v_mfma_f32_32x3
                               // of the fp16-filter + exact-rescore top-k; every `P >= ...` test below reads it as bf16)
 constexpr int RING_BF16 = 0;  // bf16 rows, 64 K per 128-byte K-tile, 8 MFMAs per phase
 constexpr int RING_X3 = 1;    // bf16x3 rows ([32 hi | 32 lo]), 32 K per K-tile, 12 MFMAs per phase
-constexpr int RING_MX = 2;    // f16mx rows (common.h), 32 K per K-tile, 4 f16 + 2 MX-fp6 MFMAs per phase;
-                              // the LDS-DMA instructions of a phase are issued inside its COMPUTE segment
-constexpr int RING_MX_EARLY = 3;  // the same with the LDS-DMA issue in the LOAD segment (as bf16 / bf16x3)
-// timing experiments on the RING_MX_EARLY stream (WRONG results): one ingredient of the loop removed
-constexpr int RING_MX_NOMFMA = 4, RING_MX_NODMA = 5, RING_MX_NOREAD = 6, RING_MX_NOBAR = 7;
-// RING_MX_EARLY with shader-clock stamps of phases P0 / P1 of the last steady-state K-tile (diagnostic)
-constexpr int RING_MX_PROF = 8;
+constexpr int RING_MX = 3;    // f16mx rows (common.h), 32 K per K-tile, 4 f16 + 2 MX-fp6 MFMAs per phase
+                              // (3, not 2: code 2 was the late-issue stream, see the header)
 
 // Geometry of one instantiation.  WM = wave rows (2 or 4); the 8 waves form a WM x (8 / WM) grid,
 // every wave owns 128 x 64 outputs, so the tile is 256 x 256 (WM = 2) or 512 x 128 (WM = 4).
@@ -190,20 +192,20 @@ struct RingRowLoader {
 // both cross terms: per 32x32 tile and K-tile 2 f16 MFMAs + 1 MX MFMA, 6 per phase, on the same LDS
 // traffic and with the same fragment addresses for both operands.
 // On return every wave has passed a workgroup barrier: the staging LDS is free.
-// GROUP (BAR1 only): the stagger group of the calling wave as a compile-time constant — the caller branches
-// ONCE on wave >> 2 into one of two copies of the loop, so that which barrier a wave crosses and at which
-// priority it computes cost no instructions inside the loop (with run-time tests — four branches and ~10 scalar
-// instructions per phase — the one-barrier schedule measured 3-8 % SLOWER than the two-barrier one).
-template <int WM, bool ODD, bool SWAP, int P = RING_BF16, bool BAR1 = false, int GROUP = -1, typename LA, typename LB>
+// GROUP: the stagger group of the calling wave as a compile-time constant — the caller branches ONCE on
+// wave >> 2 into one of two copies of the loop, so that which barrier a wave crosses and at which priority it
+// computes cost no instructions inside the loop (with run-time tests — four branches and ~10 scalar
+// instructions per phase — the schedule measured 3-8 % slower, profiles/r04_a_bar1_ab.txt).
+template <int WM, bool ODD, bool SWAP, int P, int GROUP, typename LA, typename LB>
 __device__ static inline void ring_mainloop(f32x16_t (&acc)[4][2], char* smem, int wave, int lane,
-                                            LA& la, LB& lb, int nsteps, unsigned long long* stamps = nullptr) {
+                                            LA& la, LB& lb, int nsteps) {
   using G = RingGeo<WM>;
   constexpr int NA = G::NA, NB = G::NB;
   constexpr int OFF_A0 = 0, OFF_A1 = G::A_UNIT, OFF_B0 = 2 * G::A_UNIT,
                 OFF_B1 = 2 * G::A_UNIT + G::B_UNIT;
   const int wm = wave / G::WN, wn = wave % G::WN;
-  const int group = wave >> 2;
-  static_assert(!BAR1 || GROUP == 0 || GROUP == 1, "BAR1: the caller fixes the stagger group");
+  static_assert(GROUP == 0 || GROUP == 1, "the caller fixes the stagger group");
+  static_assert(P >= RING_F16 && P <= RING_MX && P != 2, "operand arithmetic");
 
   char* const st_base = smem + wave * 1024;
   // SPLIT (512 x 128 tile: an A unit is 4 instructions, a B unit 1): the A unit is issued in two
@@ -212,25 +214,15 @@ __device__ static inline void ring_mainloop(f32x16_t (&acc)[4][2], char* smem, i
   // than a COMPUTE segment.
   constexpr bool SPLIT = NA >= 4 * NB;
   auto stage_a = [&](int buf, int h, int part) __attribute__((always_inline)) {
-    if constexpr (P == RING_MX_NODMA) return;
     char* d = st_base + buf * G::TILE + (h ? OFF_A1 : OFF_A0);
     if constexpr (SPLIT) la.stage(h, d, part * (NA / 2), (part + 1) * (NA / 2));
     else if (part == 0) la.stage(h, d, 0, NA);
   };
   auto stage_b = [&](int buf, int h) __attribute__((always_inline)) {
-    if constexpr (P == RING_MX_NODMA) return;
     lb.stage(h, st_base + buf * G::TILE + (h ? OFF_B1 : OFF_B0));
   };
 
-  constexpr bool X3 = P == RING_X3, MX = P >= RING_MX;   // (every code >= RING_MX is an f16mx stream)
-  // LATE: with 6 MFMAs (192 cycles) per phase the LOAD segment (fragment reads + 2-4 LDS-DMA issues at
-  // 100-185 cycles each next to the reads) is longer than the COMPUTE segment it is paired with, so the
-  // DMA issue moves into COMPUTE, between the MFMAs (~60 cycles each there); every counted wait then
-  // sits BEFORE its phase's issues and allows that many fewer instructions in flight.
-  constexpr bool LATE = P == RING_MX;
-  constexpr bool PROF = P == RING_MX_PROF;
-  unsigned long long st_[14] = {};
-#define RING_STAMP(i) do { if constexpr (PROF && TAIL == 0) st_[i] = __builtin_amdgcn_s_memtime(); } while (0)
+  constexpr bool X3 = P == RING_X3, MX = P == RING_MX;
   int frag_off[4];
   {
     const int row = lane & 31, half = lane >> 5, swz = (lane >> 1) & 7;
@@ -261,7 +253,6 @@ __device__ static inline void ring_mainloop(f32x16_t (&acc)[4][2], char* smem, i
     return *reinterpret_cast<const bf16x8_t*>(s + frag_off[kk]);
   };
   auto read_a = [&](int buf, int h) __attribute__((always_inline)) {
-    if constexpr (P == RING_MX_NOREAD) return;
     const char* s = rd_a + buf * G::TILE + (h ? OFF_A1 : OFF_A0);
     // Fragments in the order the MFMAs consume them (k-chunk outer), and NO lgkmcnt(0) in front of COMPUTE:
     // the compiler's own counted waits (lgkmcnt(9), (8), (7), (6), (2), (0) in an f16mx A phase) let the first
@@ -273,7 +264,6 @@ __device__ static inline void ring_mainloop(f32x16_t (&acc)[4][2], char* smem, i
       for (int i2 = 0; i2 < 2; ++i2) fa[i2][kk] = read_frag(s + i2 * 4096, kk);
   };
   auto read_b = [&](int buf, int h, bf16x8_t (&f)[4]) __attribute__((always_inline)) {
-    if constexpr (P == RING_MX_NOREAD) return;
     const char* s = rd_b + buf * G::TILE + (h ? OFF_B1 : OFF_B0);
 #pragma unroll
     for (int kk = 0; kk < 4; ++kk) f[kk] = read_frag(s, kk);
@@ -282,11 +272,8 @@ __device__ static inline void ring_mainloop(f32x16_t (&acc)[4][2], char* smem, i
   auto compute = [&](auto h_c, auto j_c, const bf16x8_t (&fb)[4], auto&& issue) __attribute__((always_inline)) {
     constexpr int h = decltype(h_c)::value, j = decltype(j_c)::value;
     __builtin_amdgcn_sched_barrier(0);
-    if constexpr (BAR1 && GROUP == 0) {   // both groups compute inside one barrier interval: the one that still
-      __builtin_amdgcn_s_setprio(2);      // has to LOAD goes first
-    } else {
-      __builtin_amdgcn_s_setprio(1);
-    }
+    // both groups compute inside one barrier interval: the one that still has to LOAD goes first
+    __builtin_amdgcn_s_setprio(GROUP == 0 ? 2 : 1);
     auto mma = [&](int i2, int ka, int kb) __attribute__((always_inline)) {
       if constexpr (P == RING_F16) {
         const f16x8_t a = __builtin_bit_cast(f16x8_t, fa[i2][ka]), b = __builtin_bit_cast(f16x8_t, fb[kb]);
@@ -298,9 +285,7 @@ __device__ static inline void ring_mainloop(f32x16_t (&acc)[4][2], char* smem, i
                  : __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i2][ka], fb[kb], acc[2 * h + i2][j], 0, 0, 0);
       }
     };
-    if constexpr (P == RING_MX_NOMFMA) {
-      asm volatile("" : "+v"(acc[2 * h][j]), "+v"(acc[2 * h + 1][j]));
-    } else if constexpr (MX) {
+    if constexpr (MX) {
       typedef __attribute__((ext_vector_type(4))) int i4;
       auto f16 = [&](int i2, int k) __attribute__((always_inline)) {
         const f16x8_t a = __builtin_bit_cast(f16x8_t, fa[i2][k]), b = __builtin_bit_cast(f16x8_t, fb[k]);
@@ -356,18 +341,14 @@ __device__ static inline void ring_mainloop(f32x16_t (&acc)[4][2], char* smem, i
   };
   auto bar = [&]() __attribute__((always_inline)) {
     __builtin_amdgcn_sched_barrier(0);
-    if constexpr (P != RING_MX_NOBAR) __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
   };
-  // the barrier in front of (g = 0) / behind (g = 1) a COMPUTE segment: with BAR1 only group g crosses it
+  // the barrier in front of (g = 0) / behind (g = 1) a COMPUTE segment: only group g crosses it
   auto bar_g = [&](int g) __attribute__((always_inline)) {
-    if constexpr (BAR1) {
-      __builtin_amdgcn_sched_barrier(0);
-      if (GROUP == g) __builtin_amdgcn_s_barrier();
-      __builtin_amdgcn_sched_barrier(0);
-    } else {
-      bar();
-    }
+    __builtin_amdgcn_sched_barrier(0);
+    if (GROUP == g) __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_sched_barrier(0);
   };
 
   using I0 = std::integral_constant<int, 0>;
@@ -393,9 +374,6 @@ __device__ static inline void ring_mainloop(f32x16_t (&acc)[4][2], char* smem, i
   bar();
   read_b(0, 0, fbx);
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  if constexpr (!BAR1) {
-    if (group == 1) bar();  // group 1 runs one barrier behind group 0
-  }
 
   // One K-tile = 4 phases.  PAR = tile parity (LDS buffer; which register set holds B0).
   // TAIL: 0 = steady state, 1 = tile nsteps-2, 2 = tile nsteps-1 (nothing left to stage).
@@ -409,80 +387,60 @@ __device__ static inline void ring_mainloop(f32x16_t (&acc)[4][2], char* smem, i
     constexpr int TAIL = decltype(tail_c)::value;
     bf16x8_t(&b0)[4] = PAR ? fby : fbx;  // B0 of this tile
     bf16x8_t(&b1)[4] = PAR ? fbx : fby;  // B1 of this tile; from P3 on: B0 of the next tile
-    // A phase = reads; [early: issues;] counted wait; barrier; COMPUTE [late: issues inside]; barrier.
-    // `cnt` = what the wait allows in flight when it stands AFTER the phase's `n_issue` instructions.
-    // `prep` (EARLY schedules): the K-cursor advance of the NEXT phase's issue — scalar code with branches,
-    // ~100 cycles at the head of a LOAD segment (RING_MX_PROF: LDS-DMA issue 172 cycles in P1 against 64
-    // in P0) — runs between the MFMAs of this phase instead, where the wave waits for the matrix pipe anyway.
-    auto phase = [&](auto cnt_c, auto n_issue_c, auto h_c, auto j_c, const bf16x8_t (&fb)[4], auto&& issue,
-                     auto sb_c, auto&& prep) __attribute__((always_inline)) {
-      constexpr int CNT = decltype(cnt_c)::value, NI = decltype(n_issue_c)::value;
-      constexpr int SB = decltype(sb_c)::value;   // first stamp slot of this phase, -1 = none
-      if constexpr (!LATE) {
-        if constexpr (SB >= 0) RING_STAMP(SB + 1);       // reads issued
-        issue();
-        if constexpr (SB >= 0) RING_STAMP(SB + 2);       // LDS-DMA issued
-        if constexpr (CNT >= 0) wait_vmcnt<CNT>();
-        if constexpr (SB >= 0) RING_STAMP(SB + 3);       // counted wait passed
-        bar_g(0);
-        if constexpr (SB >= 0) RING_STAMP(SB + 4);       // barrier passed: COMPUTE starts
-        compute(h_c, j_c, fb, prep);
-        if constexpr (SB >= 0) RING_STAMP(SB + 5);       // MFMAs issued
-      } else {
-        if constexpr (CNT >= 0) wait_vmcnt<(CNT - NI)>();
-        bar_g(0);
-        compute(h_c, j_c, fb, issue);
-      }
+    // A phase (after its reads) = issues; counted wait; group 0's barrier; COMPUTE; group 1's barrier.
+    // `cnt` = what the wait allows in flight behind the phase's own issues, -1 = no wait.
+    // `prep`: the K-cursor advance of the NEXT phase's issue — scalar code with branches, ~100 cycles at the
+    // head of a LOAD segment (LDS-DMA issue measured 172 cycles in P1 against 64 in P0) — runs between the
+    // MFMAs of this phase instead, where the wave waits for the matrix pipe anyway.
+    auto phase = [&](auto cnt_c, auto h_c, auto j_c, const bf16x8_t (&fb)[4], auto&& issue,
+                     auto&& prep) __attribute__((always_inline)) {
+      constexpr int CNT = decltype(cnt_c)::value;
+      issue();
+      if constexpr (CNT >= 0) wait_vmcnt<CNT>();
+      bar_g(0);
+      compute(h_c, j_c, fb, prep);
       bar_g(1);
-      if constexpr (SB >= 0) RING_STAMP(SB + 6);         // closing barrier passed
     };
 #define RING_IC(x) std::integral_constant<int, (x)> {}
-    constexpr int HA = SPLIT ? NA / 2 : NA;   // instructions of the A issue in P0 / P2
-    constexpr int HB = SPLIT ? NA / 2 : 0;    // A instructions issued next to the B unit in P1 / P3
     // P0: A0 x B0
-    RING_STAMP(0);
     read_a(PAR, 0);
     if constexpr (TAIL <= 1)
-      phase(RING_IC(3 * NA + 2 * NB - (SPLIT ? NA / 2 : 0)), RING_IC(HA), I0{}, I0{}, b0,
-            [&] { stage_a(PAR ^ 1, 1, 0); }, RING_IC(0),  // A1(t+1) (SPLIT: its first half)
-            [&] { if constexpr (TAIL == 0 && !LATE) lb.begin_tile(); });
+      phase(RING_IC(3 * NA + 2 * NB - (SPLIT ? NA / 2 : 0)), I0{}, I0{}, b0,
+            [&] { stage_a(PAR ^ 1, 1, 0); },  // A1(t+1) (SPLIT: its first half)
+            [&] { if constexpr (TAIL == 0) lb.begin_tile(); });   // (for P1's B0(t+2))
     else
-      phase(RING_IC(NA), RING_IC(0), I0{}, I0{}, b0, [] {}, RING_IC(-1), [] {});
+      phase(RING_IC(NA), I0{}, I0{}, b0, [] {}, [] {});
     // P1: A0 x B1
-    RING_STAMP(7);
     read_b(PAR, 1, b1);
     if constexpr (TAIL == 0)
-      phase(RING_IC(2 * NA + 3 * NB), RING_IC(HB + NB), I0{}, I1{}, b1, [&] {
+      phase(RING_IC(2 * NA + 3 * NB), I0{}, I1{}, b1, [&] {
         stage_a(PAR ^ 1, 1, 1);  // SPLIT: second half of A1(t+1)
-        if constexpr (LATE) lb.begin_tile();   // (EARLY: advanced in P0's COMPUTE)
         stage_b(PAR, 0);  // B0(t+2)
-      }, RING_IC(7), [&] { if constexpr (!LATE) la.begin_tile(); });
+      }, [&] { la.begin_tile(); });   // (for P2's A0(t+2))
     else if constexpr (TAIL == 1)
-      phase(RING_IC(2 * NA + 2 * NB), RING_IC(HB), I0{}, I1{}, b1, [&] { stage_a(PAR ^ 1, 1, 1); }, RING_IC(-1), [] {});
+      phase(RING_IC(2 * NA + 2 * NB), I0{}, I1{}, b1, [&] { stage_a(PAR ^ 1, 1, 1); }, [] {});
     else
-      phase(RING_IC(0), RING_IC(0), I0{}, I1{}, b1, [] {}, RING_IC(-1), [] {});
+      phase(RING_IC(0), I0{}, I1{}, b1, [] {}, [] {});
     // P2: A1 x B1
     read_a(PAR, 1);
     if constexpr (TAIL == 0)
-      phase(RING_IC(3 * NA + 2 * NB - (SPLIT ? NA / 2 : 0)), RING_IC(HA), I1{}, I1{}, b1, [&] {
-        if constexpr (LATE) la.begin_tile();   // (EARLY: advanced in P1's COMPUTE)
-        stage_a(PAR, 0, 0);  // A0(t+2) (SPLIT: its first half)
-      }, RING_IC(-1), [] {});
+      phase(RING_IC(3 * NA + 2 * NB - (SPLIT ? NA / 2 : 0)), I1{}, I1{}, b1,
+            [&] { stage_a(PAR, 0, 0); }, [] {});  // A0(t+2) (SPLIT: its first half)
     else if constexpr (TAIL == 1)
-      phase(RING_IC(2 * NA + NB), RING_IC(0), I1{}, I1{}, b1, [] {}, RING_IC(-1), [] {});
+      phase(RING_IC(2 * NA + NB), I1{}, I1{}, b1, [] {}, [] {});
     else
-      phase(RING_IC(-1), RING_IC(0), I1{}, I1{}, b1, [] {}, RING_IC(-1), [] {});
+      phase(RING_IC(-1), I1{}, I1{}, b1, [] {}, [] {});
     // P3: A1 x B0   (B0 of the next tile goes into the register set B1 just vacated)
     if constexpr (TAIL <= 1) read_b(PAR ^ 1, 0, b1);
     if constexpr (TAIL == 0)
-      phase(RING_IC(2 * NA + 3 * NB), RING_IC(HB + NB), I1{}, I0{}, b0, [&] {
+      phase(RING_IC(2 * NA + 3 * NB), I1{}, I0{}, b0, [&] {
         stage_a(PAR, 0, 1);  // SPLIT: second half of A0(t+2)
         stage_b(PAR, 1);     // B1(t+2)
-      }, RING_IC(-1), [] {});
+      }, [] {});
     else if constexpr (TAIL == 1)
-      phase(RING_IC(NA + NB), RING_IC(0), I1{}, I0{}, b0, [] {}, RING_IC(-1), [] {});
+      phase(RING_IC(NA + NB), I1{}, I0{}, b0, [] {}, [] {});
     else
-      phase(RING_IC(-1), RING_IC(0), I1{}, I0{}, b0, [] {}, RING_IC(-1), [] {});
+      phase(RING_IC(-1), I1{}, I0{}, b0, [] {}, [] {});
 #undef RING_IC
   };
   for (int t = 0; t + 3 < nsteps; t += 2) {  // pairs of steady-state tiles
@@ -497,17 +455,7 @@ __device__ static inline void ring_mainloop(f32x16_t (&acc)[4][2], char* smem, i
     ktile(I0{}, I1{});
     ktile(I1{}, I2{});
   }
-  if constexpr (!BAR1) {
-    if (group == 0) bar();
-  }
   __syncthreads();
-  if constexpr (PROF) {
-    if (stamps != nullptr && lane == 0 && (wave & 3) == 0) {
-#pragma unroll
-      for (int i = 0; i < 14; ++i) stamps[(wave >> 2) * 14 + i] = st_[i];
-    }
-  }
-#undef RING_STAMP
 }
 
 }  // namespace oibl

@@ -46,9 +46,8 @@ from openibl_amd import lib  # noqa: E402
 h = lib.debug_hooks()
 run(3)
 run(48)            # (the first extraction of a process is slower: not one of the cases)
-for guard, bar1, splitk in ((True, 1, 1), (False, 1, 1), (True, 1, 1), (False, 1, 1), (True, 1, 1), (False, 1, 1)):
+for guard, splitk in ((True, 1), (False, 1), (True, 1), (False, 1), (True, 1), (False, 1)):
     extract.GUARD_REPLAYS = guard
-    h.oibl_debug_set_ring_bar1(bar1)
     h.oibl_debug_set_mx_splitk(splitk)
     extract.release_graphs(model)
     run(3)
@@ -61,6 +60,6 @@ for guard, bar1, splitk in ((True, 1, 1), (False, 1, 1), (True, 1, 1), (False, 1
     run(3)
     rate_res, _ = run(48)
     pinned[:] = host
-    print(f"guard {guard} bar1 {bar1} splitk {splitk}: {rate:7.1f} images/s from pinned fp32 host batches, {rate_res:7.1f} from "
+    print(f"guard {guard} splitk {splitk}: {rate:7.1f} images/s from pinned fp32 host batches, {rate_res:7.1f} from "
           f"resident batches ({100 * rate / rate_res:.1f} %)", flush=True)
 dist.destroy_process_group()

@@ -242,37 +242,71 @@ def test_hot_kernels_stay_inside_their_register_budgets():
 
 def test_hot_kernels_hold_exactly_their_matrix_instructions():
     """The TEXT of the hot kernels, from the gfx950 code objects of the current build (openibl_amd.build.kernel_text):
-    a ring kernel holds one copy of its K loop and one peeled pair of last K-tiles per stagger-group body — 16
-    phases (20 with an odd number of K-tiles) of 8 (bf16), 12 (bf16x3) or 6 (f16mx) matrix instructions, twice that
-    with one body per group (BAR1).  More means the compiler has cloned the body: in round 4 three correlated
-    branches on a diagnostic flag did, and the product step lost 4.5 % with the flag off."""
+    a ring kernel holds one body per stagger group, and a body one copy of its K loop and one peeled pair of last
+    K-tiles — 16 phases (20 with an odd number of K-tiles) of 8 (bf16), 12 (bf16x3) or 6 (f16mx) matrix instructions.
+    More means the compiler has cloned the body: in round 4 three correlated branches on a diagnostic flag did, and
+    the product step lost 4.5 % with the flag off.  The product library holds exactly the instantiations the dispatch
+    can launch: a kernel more is an experiment that shipped."""
     import re
     from openibl_amd import build
     text = build.kernel_text()
     if not text:
         import pytest
         pytest.skip("llvm-objdump / clang-offload-bundler not found next to hipcc")
-    per_phase = {0: 8, 1: 12, 2: 6, 3: 6, 4: 0, 5: 6, 6: 6, 7: 6, 8: 6}
-    ring = 0
-    for name, t in text.items():
-        m = re.search(r"conv3x3_ring_kernelILi(\d)ELb([01])ELb([01])ELi(\d)ELb([01])ELb([01])EEE", name)
-        if m and not name.endswith(".kd"):
-            odd, p, bar1 = int(m.group(3)), int(m.group(4)), int(m.group(6))
-            want = per_phase[p] * (20 if odd else 16) * (2 if bar1 else 1)
-            assert t["mfma"] == want, (name, t, want)
-            assert t["bytes"] < 64 * 1024, (name, t)          # the instruction cache two CUs share
-            ring += 1
-    assert ring >= 40
+    per_phase = {0: 8, 1: 12, 3: 6}      # operand codes of ring_core.h: bf16, bf16x3, f16mx
+
+    def family(stem):
+        return {n: t for n, t in text.items() if re.search(stem + r"I", n) and not n.endswith(".kd")}
+
+    # convolutions: wave rows {2, 4} x pooled or not x the three arithmetics (f16mx operands write f16mx lines), and
+    # the odd K-tile count that only bf16 Cin = 64 has, on the 512 x 128 tile
+    ring = {}
+    for name, t in family("conv3x3_ring_kernel").items():
+        m = re.search(r"conv3x3_ring_kernelILi(\d)ELb([01])ELb([01])ELi(\d)ELb([01])EEE", name)
+        assert m, name
+        wm, pool, odd, p, outmx = (int(g) for g in m.groups())
+        ring[(wm, pool, odd, p, outmx)] = t
+        assert t["mfma"] == per_phase[p] * (20 if odd else 16) * 2, (name, t)
+        assert t["bytes"] < 64 * 1024, (name, t)          # the instruction cache two CUs share
+    want = {(wm, pool, 0, p, int(p == 3)) for wm in (2, 4) for pool in (0, 1) for p in per_phase}
+    want |= {(4, pool, 1, 0, 0) for pool in (0, 1)}
+    assert set(ring) == want and len(family("conv3x3_ring_kernel")) == 14, sorted(ring)
+    # distances: filter pass or full matrix x the three arithmetics, 16 phases per group body
+    pair = {}
+    for name, t in family("pairwise_ring_kernel").items():
+        m = re.search(r"pairwise_ring_kernelILb([01])ELi(\d)EEE", name)
+        assert m, name
+        pair[(int(m.group(1)), int(m.group(2)))] = t
+        assert t["mfma"] == per_phase[int(m.group(2))] * 32, (name, t)
+    assert set(pair) == {(f, p) for f in (0, 1) for p in per_phase} and len(family("pairwise_ring_kernel")) == 6, sorted(pair)
     # the 4-wave halo kernel of the 128-output-channel layers: 18 K-tiles x 4 phases x 6, one body; the fp16 filter
     # pass of the f16r top-k: the bf16 ring loop (16 phases x 8) per stagger-group body
-    halo4 = {n: t for n, t in text.items() if "conv3x3_halo4_kernel" in n and not n.endswith(".kd")}
+    halo4 = family("conv3x3_halo4_kernel")
     assert len(halo4) == 2 and all(t["mfma"] == 432 and t["bytes"] < 64 * 1024 for t in halo4.values()), halo4
-    f16r = {n: t for n, t in text.items() if "pairwise_f16r_kernel" in n and not n.endswith(".kd")}
-    assert len(f16r) == 4 and all(t["mfma"] == (256 if re.search(r"ELb1EEE", n) else 128) for n, t in f16r.items()), f16r
+    f16r = family("pairwise_f16r_kernel")
+    assert len(f16r) == 2 and all(t["mfma"] == 256 for t in f16r.values()), f16r
     # the packed PCA stream: 32 tiles x 4 k-pairs per chunk, a generic and a last-chunk body
     pk = {n: t for n, t in text.items() if "pca_stream_kernel" in n and not n.endswith(".kd")}
     assert pk and all(t["mfma"] == 256 for t in pk.values()), pk
-    halo = {n: t for n, t in text.items() if "conv3x3_halo_kernel" in n and not n.endswith(".kd")}
-    assert halo and all(t["mfma"] == (864 if re.search(r"ELb1EEE", n) else 432) for n, t in halo.items()), halo
+    # the 8-wave halo kernel: 18 K-tiles x 4 phases x 6 per stagger-group body, pooled or not
+    halo = family("conv3x3_halo_kernel")
+    assert len(halo) == 2 and all(t["mfma"] == 864 for t in halo.values()), halo
     stems = {n: t["mfma"] for n, t in text.items() if "vgg_stem" in n and not n.endswith(".kd")}
     assert sorted(set(stems.values())) == [126, 168, 234], stems
+
+
+def test_mx_variant_hook_takes_only_the_routes_that_exist():
+    """oibl_debug_set_mx_variant (debug library): 0 = default dispatch, 1 = ring kernels only, 3 = halo kernel
+    wherever legal.  The codes of the removed experiments (late issue, timing loops, stamps, halo4 everywhere, the
+    halo kernel's first waits) are refused with an error status and leave the selection as it was."""
+    from openibl_amd import lib
+    h = lib.debug_hooks()
+    try:
+        for v in (0, 1, 3):
+            assert h.oibl_debug_set_mx_variant(v) == 0, v
+        for v in (2, 4, 5, 6, 7, 8, 13, 19, -1):
+            assert h.oibl_debug_set_mx_variant(v) == -1, v          # OIBL_E_INVALID
+        assert b"mx_variant" in h.oibl_last_error()
+    finally:
+        h.oibl_debug_set_mx_variant(0)
+        lib.use_product_library()

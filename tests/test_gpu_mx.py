@@ -63,11 +63,10 @@ def _mx_out(y, which=0):
     return ops.nhwc_to_nchw_f32(ops.mx_join(y, which)).cpu()
 
 
-@pytest.fixture(params=[0, 1, 3, 2], ids=["auto", "ring", "halo", "ring-late"])
+@pytest.fixture(params=[0, 1, 3], ids=["auto", "ring", "halo"])
 def mx_variant(request):
     """0 = default dispatch (halo kernel for the 256-output-channel layers, ring kernels elsewhere), 1 = ring
-    kernels only, 3 = halo kernel wherever it applies, 2 = ring kernels with the LDS-DMA issue inside the
-    COMPUTE segments."""
+    kernels only, 3 = halo kernel wherever it applies."""
     from openibl_amd import lib
     lib.debug_hooks().oibl_debug_set_mx_variant(request.param)
     yield request.param
