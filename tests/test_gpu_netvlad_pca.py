@@ -1,8 +1,11 @@
 """NetVLAD aggregation and PCA projection kernels against the oracle (GPU)."""
+from contextlib import contextmanager
+
 import pytest
 import torch
 
 from conftest import assert_rel_l2, load_golden
+from helpers import head_forward_ref as hf
 from openibl_amd import ops, synth
 from oracle import descriptor as od
 
@@ -140,6 +143,110 @@ def test_pca_packed_weight_streaming_kernel(dev):
     v2 = torch.randn((5, 8192), generator=g).to(dev)
     got = ops.pca(v2, ops.PcaWeight(w2), b2)
     assert_rel_l2("packed 8192 -> 256", got.cpu(), od.pca_project(v2.cpu().double(), w2.cpu().double(), b2.cpu().double()), 5e-6)
+
+
+# ---- PCA off the production shape (cases and their arithmetic: tests/test_head_forward_cases_cpu.py) ---------------------
+PCA_TOL = 5e-6
+
+
+def _pca_both(name, v, w, b, bf16=False):
+    """ops.pca with and without the L2 norm against fp64 at the file's bar; returns the normalised output.  `w` may
+    be a PcaWeight; the oracle takes its rows."""
+    rows = (w.rows if isinstance(w, ops.PcaWeight) else w).float().cpu()
+    out = ops.pca(v, w, b)
+    raw = ops.pca(v, w, b, l2norm=False)
+    assert_rel_l2(f"{name}, normalised", out.cpu(), hf.pca_oracle(v.cpu(), rows, b.cpu(), bf16), PCA_TOL)
+    assert_rel_l2(f"{name}, projection only", raw.cpu(), hf.pca_oracle(v.cpu(), rows, b.cpu(), bf16, l2norm=False), PCA_TOL)
+    return out
+
+
+@contextmanager
+def _pca_hook(name, value, default=1):
+    from openibl_amd import lib
+    setter = getattr(lib.debug_hooks(), f"oibl_debug_set_{name}")
+    setter(value)
+    try:
+        yield
+    finally:
+        setter(default)
+
+
+@pytest.mark.parametrize("D,d", [(4096, 128), (8192, 384)])
+def test_pca_streaming_kernel_off_size(dev, D, d):
+    """pca_small_kernel at one and at two trips of its K loop, fewer output dims than a full grid: the oracle's
+    numbers; row 0 of the two-row call is the one-row call; hook off, the MFMA tile gives the same within the bar."""
+    assert hf.pca_small_ok(2, D, d)
+    v, w, b = (t.to(dev) for t in hf.pca_problem(D + d, 2, D, d))
+    outs = {n: _pca_both(f"pca streaming {D}->{d} N={n}", v[:n].contiguous(), w, b) for n in (1, 2)}
+    assert torch.equal(outs[1], outs[2][:1]), "row 0 of N=2 differs from N=1"
+    with _pca_hook("pca_small", 0):
+        tile = _pca_both(f"pca tile (hook) {D}->{d} N=2", v, w, b)
+    assert not torch.equal(tile, outs[2])                 # (the hook did select the other kernel)
+
+
+@pytest.mark.parametrize("N", [1, 2])
+@pytest.mark.parametrize("D", [4128, 2048])
+def test_pca_tile_where_the_streaming_kernel_refuses(dev, D, N):
+    """D = 4128: 129 K-steps, one split; D = 2048: 64 K-steps in four splits.  One and two fp32 rows on the tile."""
+    assert not hf.pca_small_ok(N, D, 128) and hf.pca_splits(N, D, 128)[1] == (1 if D == 4128 else 4)
+    v, w, b = (t.to(dev) for t in hf.pca_problem(D + N, N, D, 128))
+    out = _pca_both(f"pca tile {D}->128 N={N}", v, w, b)
+    with _pca_hook("pca_small", 0):
+        assert torch.equal(ops.pca(v, w, b), out)         # the tile already: the hook changes nothing
+
+
+@pytest.mark.parametrize("D", [2112, 4096])
+def test_pca_bf16_tile_off_size(dev, D):
+    """bf16 weights, 5 rows, d = 256: 33 K-steps (one split) and 64 (four)."""
+    assert hf.pca_splits(5, D, 256, bf16=True)[1] == (1 if D == 2112 else 4)
+    v, w, b = (t.to(dev) for t in hf.pca_problem(D, 5, D, 256))
+    _pca_both(f"pca bf16 tile {D}->256 N=5", v, ops.cast(w, "bf16"), b, bf16=True)
+
+
+@pytest.mark.parametrize("precision", ["fp32", "bf16"])
+def test_pca_ragged_row_tiles(dev, precision):
+    """31, 32, 33, 64 and 65 rows of 2048 -> 256: a tile one row short, full, one row over, two tiles, two and a row.
+    The split plan is the same for all of them, so row i is the same bits whatever N."""
+    bf16 = precision == "bf16"
+    Ns = (31, 32, 33, 64, 65)
+    assert len({hf.pca_splits(n, 2048, 256, bf16) for n in Ns}) == 1
+    v, w, b = (t.to(dev) for t in hf.pca_problem(2048, 65, 2048, 256))
+    wd = ops.cast(w, precision)
+    outs = {n: _pca_both(f"pca {precision} 2048->256 N={n}", v[:n].contiguous(), wd, b, bf16) for n in Ns}
+    for n in Ns[:-1]:
+        assert torch.equal(outs[n], outs[65][:n]), f"rows of the N={n} call differ from the N=65 call"
+
+
+@pytest.mark.parametrize("D,d", [(16384, 256), (8192, 768), (8192, 4352)])
+def test_pca_packed_stream_off_size(dev, D, d):
+    """The packed stream (ops.PcaWeight, 3 and 32 rows): two chunks per K part (16384: the branch of a chunk that
+    is not the last), d = 768 (the one-launch reduction clamps its loads), d = 4352 (> 4096: the two-launch reduction
+    over 16 partials)."""
+    assert hf.pca_stream_ok(3, D, d) and hf.pca_stream_ok(32, D, d)
+    v, w, b = (t.to(dev) for t in hf.pca_problem(D + d, 32, D, d))
+    pw = ops.PcaWeight(w)
+    outs = {n: _pca_both(f"pca packed {D}->{d} N={n}", v[:n].contiguous(), pw, b) for n in (3, 32)}
+    assert pw._packed is not None
+    assert torch.equal(outs[3], outs[32][:3]), "rows 0..2 of the 32-row call differ from the 3-row call"
+    assert not torch.equal(outs[32], ops.pca(v, w, b))    # (the holder did select the packed stream)
+    if D == 16384:
+        for hook in (2, 3):                               # the 8-wave instantiations: 32 partials, two launches
+            with _pca_hook("pca_stream", hook):
+                deep = {n: _pca_both(f"pca packed (hook {hook}) {D}->{d} N={n}", v[:n].contiguous(), pw, b) for n in (3, 32)}
+            assert torch.equal(deep[3], deep[32][:3]) and not torch.equal(deep[32], outs[32])
+
+
+@pytest.mark.parametrize("route", ["tile", "packed, one launch", "packed, d > 4096"])
+def test_pca_zero_row_meets_the_eps_clamp(dev, route):
+    """An all-zero input row with b = 0 projects to zero: 0 / max(0, 1e-12) = 0, no NaN, through each of the three
+    reductions; its neighbours are untouched."""
+    D, d = {"tile": (2048, 256), "packed, one launch": (8192, 768), "packed, d > 4096": (8192, 4352)}[route]
+    v, w, _ = hf.pca_problem(D + d + 1, 3, D, d)
+    v[1] = 0.0
+    v, w, b = v.to(dev), w.to(dev), torch.zeros(d, device=dev)
+    out = _pca_both(f"pca zero row, {route}", v, w if route == "tile" else ops.PcaWeight(w), b)
+    assert torch.isfinite(out).all() and float(out[1].abs().max()) == 0.0
+    assert float(out[0].abs().max()) > 0 and float(out[2].abs().max()) > 0
 
 
 @pytest.mark.parametrize("precision", ["fp32", "bf16"])
