@@ -76,7 +76,7 @@ __global__ __launch_bounds__(256) void nvb_aggregate_kernel(const float* __restr
 // multiplies every fp32 rounding of a contribution by that factor.
 __global__ __launch_bounds__(256) void nvb_rowstats_kernel(const float* __restrict__ V, const float* __restrict__ G,
                                                            double* __restrict__ st, long rows) {
-  constexpr int C = VLB_C;
+  constexpr int C = VLAD_C;
   const int lane = threadIdx.x & 63;
   const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
@@ -95,7 +95,7 @@ __global__ __launch_bounds__(256) void nvb_rowstats_kernel(const float* __restri
   for (int i = 0; i < 8; ++i) ss += vv[i] * vv[i];
   ss = wave_sum_f64(ss);
   const double t = sqrt(ss);
-  const double it = 1.0 / fmax(t, (double)VLB_EPS);
+  const double it = 1.0 / fmax(t, (double)VLAD_EPS);
   double s2 = 0.0, ug = 0.0;
 #pragma unroll
   for (int i = 0; i < 8; ++i) {
@@ -118,7 +118,7 @@ __global__ __launch_bounds__(256) void nvb_dv_kernel(float* __restrict__ V, cons
                                                      const double* __restrict__ st, const double* __restrict__ A,
                                                      const float* __restrict__ centroids, float* __restrict__ dvc,
                                                      double* __restrict__ dCp, long rows) {
-  constexpr int C = VLB_C, K = VLB_K;
+  constexpr int C = VLAD_C, K = VLAD_K;
   const int lane = threadIdx.x & 63;
   const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
@@ -128,12 +128,12 @@ __global__ __launch_bounds__(256) void nvb_dv_kernel(float* __restrict__ V, cons
   const double S2 = wave_sum_f64(st[3 * (n * K + lane) + 1]);
   const double UG = wave_sum_f64(st[3 * (n * K + lane) + 2]);
   const double gn = sqrt(S2);
-  const bool g_clamped = gn < (double)VLB_EPS;
-  const double ig = 1.0 / fmax(gn, (double)VLB_EPS);
+  const bool g_clamped = gn < (double)VLAD_EPS;
+  const double ig = 1.0 / fmax(gn, (double)VLAD_EPS);
   const double yg = g_clamped ? 0.0 : UG * ig;                      // <Y, G>; a clamped g is a constant
   const double t = st[3 * row];
-  const bool t_clamped = t < (double)VLB_EPS;
-  const double it = 1.0 / fmax(t, (double)VLB_EPS);
+  const bool t_clamped = t < (double)VLAD_EPS;
+  const double it = 1.0 / fmax(t, (double)VLAD_EPS);
   float* v = V + row * C;
   const float* g = G + row * C;
   const float* c = centroids + (size_t)k * C;
@@ -197,7 +197,7 @@ extern "C" {
 
 // workspace: vlad_backward_layout with one unit (the image) and one normalised vector per image
 size_t oibl_netvlad_backward_workspace_bytes(int N, int P, int K, int C, int want_grad_feat) {
-  if (N <= 0 || P <= 0 || K != VLB_K || C != VLB_C) return 0;
+  if (N <= 0 || P <= 0 || K != VLAD_K || C != VLAD_C) return 0;
   return vlad_backward_layout(N, P, 1, 1, want_grad_feat).total;
 }
 
@@ -208,8 +208,8 @@ int oibl_netvlad_backward(const void* feat, int N, int P, int K, int C, int prec
   OIBL_REQUIRE(feat && assign_w && centroids && grad_vlad_norm && ws, "netvlad_backward: null pointer");
   OIBL_REQUIRE(grad_assign_w || grad_centroids || grad_feat, "netvlad_backward: no output requested");
   OIBL_REQUIRE(precision == OIBL_F32, "netvlad_backward: the feature map must be fp32 (got precision %d)", precision);
-  OIBL_REQUIRE(K == VLB_K, "netvlad_backward: kernels are built for num_clusters = 64 (got %d)", K);
-  OIBL_REQUIRE(C == VLB_C, "netvlad_backward: kernels are built for dim = 512 (got %d)", C);
+  OIBL_REQUIRE(K == VLAD_K, "netvlad_backward: kernels are built for num_clusters = 64 (got %d)", K);
+  OIBL_REQUIRE(C == VLAD_C, "netvlad_backward: kernels are built for dim = 512 (got %d)", C);
   OIBL_REQUIRE(N > 0 && P > 0, "netvlad_backward: bad shape N=%d P=%d", N, P);
   OIBL_REQUIRE(N <= 65535, "netvlad_backward: at most 65535 images per call (got %d)", N);
   OIBL_REQUIRE((uintptr_t)feat % 16 == 0 && (uintptr_t)assign_w % 16 == 0 && (uintptr_t)centroids % 16 == 0 &&
@@ -270,7 +270,7 @@ int oibl_netvlad_backward(const void* feat, int N, int P, int K, int C, int prec
     OIBL_LAUNCH_CHECK();
   }
   if (grad_assign_w || grad_centroids) {
-    hipLaunchKernelGGL(nvb_reduce_kernel, dim3(VLB_K * VLB_C / 256), dim3(256), 0, st, (const float*)dWp,
+    hipLaunchKernelGGL(nvb_reduce_kernel, dim3(VLAD_K * VLAD_C / 256), dim3(256), 0, st, (const float*)dWp,
                        (const double*)dCp, grad_assign_w, grad_centroids, N);
     OIBL_LAUNCH_CHECK();
   }

@@ -8,12 +8,10 @@
 // each intra-normalised per cluster and L2-normalised over the K*C vector; the score of an (anchor, pair) couple is
 // the 9 x 9 table of dots of their region vectors.  Three pieces, four launches, the map read ONCE:
 //
-//   region_aggregate_kernel  netvlad_fused_kernel's scheme (netvlad.hip: chunks of 32 pixels x 512 channels in LDS,
-//                            1 / |x_p|, logits and aggregation on v_mfma_f32_32x32x2_f32, softmax over the 64
-//                            clusters, accumulators kept across the slab) on slabs of pixels that lie inside ONE
-//                            quarter: pixel i of quarter q is map pixel (q / 2 * h/2 + i / (w/2)) * w + q % 2 * w/2 +
-//                            i % (w/2) — a pixel is 2 KB contiguous in the NHWC map, so the gather costs no
-//                            coalescing.  Writes parts[n][q][slab][64][512] = acc - (sum_p a[p][k]) centroids[k][c].
+//   region_aggregate_kernel  netvlad_fused_kernel's body (vlad_fused_slab, vlad_forward_core.h) over QuarterSlabs:
+//                            slabs of pixels that lie inside ONE quarter, a quarter's pixel placed in the map by
+//                            quarter_map_pixel (vlad_common.h, shared with the backward).  Writes
+//                            parts[n][q][slab][64][512] = acc - (sum_p a[p][k]) centroids[k][c].
 //   region_rowstats_kernel   one wave per (image, cluster) row: the slabs of each quarter added in slab order, the
 //                            quarters added in the order listed above, per region the intra-norm of the row — written
 //                            to the output — and the row's share of the vector's squared norm;
@@ -21,19 +19,12 @@
 //   region_score_kernel      one workgroup per (tuple, pair, pair region): 9 dots of length K*C against the anchor's
 //                            regions (the anchor's 9 x 128 KB stay in L2 across the tuple's pairs), fixed-order sums.
 //
-// The aggregation kernel repeats netvlad_fused_kernel's body instead of sharing it: the eval head's code object is
-// pinned (its descriptors are compared bit for bit across releases), and the two differ in how a pixel index becomes
-// an address, where the slab ends and where the partial goes — a shared body would branch on its caller in all three.
-//
 // The slab decomposition is a function of the map size alone and nothing is accumulated with atomics: an image's
 // region vectors and a pair's scores are bit-identical whatever batch they are computed in.  fp32 arithmetic throughout.
-#include "gemm_core.h"
+#include "vlad_forward_core.h"
 
 namespace oibl {
 
-constexpr int RG_XP = 516;           // floats per LDS row of the chunk: 16-byte aligned, +4 banks per pixel
-constexpr int RG_LP = 65;            // pitch of the [32][64] logit / assignment tiles
-constexpr int RG_LDS = (32 * RG_XP + 4 * 32 * RG_LP + 2 * 32 * RG_LP + 32 + 64) * 4;
 constexpr int RG_SLAB_TARGET = 64;   // pixels per slab, at most: two chunks
 
 __global__ __launch_bounds__(256) void region_aggregate_kernel(const float* __restrict__ feat,
@@ -41,182 +32,7 @@ __global__ __launch_bounds__(256) void region_aggregate_kernel(const float* __re
                                                                const float* __restrict__ centroids,
                                                                float* __restrict__ parts, int hq, int wq, int nslab,
                                                                int slab_px, int normalize) {
-  constexpr int C = 512;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* const x_s = reinterpret_cast<float*>(smem);             // [32][RG_XP]
-  float* const lp_s = x_s + 32 * RG_XP;                           // [4 waves][32][RG_LP] partial logits
-  float* const a_s = lp_s + 4 * 32 * RG_LP;                       // [32][RG_LP] a[p][k]
-  float* const a2_s = a_s + 32 * RG_LP;                           // [32][RG_LP] a[p][k] / |x_p|
-  float* const inv_s = a2_s + 32 * RG_LP;                         // [32]
-  float* const cs_s = inv_s + 32;                                 // [64] sum_p a[p][k] of the slab
-  const int n = blockIdx.x;
-  const int quarter = (int)blockIdx.y / nslab, slab = (int)blockIdx.y % nslab;
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int l31 = lane & 31, kh = lane >> 5;
-  const int Pq = hq * wq;                                         // pixels of a quarter
-  const int p_lo = slab * slab_px;
-  int p_hi = p_lo + slab_px;
-  if (p_hi > Pq) p_hi = Pq;
-  const int wfull = 2 * wq;
-  // first pixel of this quarter in the image's map
-  const float* fimg = feat + ((size_t)n * 4 * Pq + (size_t)(quarter >> 1) * hq * wfull + (size_t)(quarter & 1) * wq) * C;
-
-  f32x16_t acc[2][4];          // [cluster tile][channel tile of this wave's 128 channels]
-#pragma unroll
-  for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-    for (int ct = 0; ct < 4; ++ct)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[kt][ct][r] = 0.f;
-  float colsum = 0.f;          // threads 0..63
-  // the assignment weights of this wave's 128 channels stay in registers for the whole slab: lane (cluster l31 /
-  // 32 + l31, k half kh) holds w[cluster][128 wave + 8 j + 4 kh ..+3]
-  float4 wr[2][16];
-  {
-    const float* wb = w + (size_t)l31 * C + 128 * wave + 4 * kh;
-#pragma unroll
-    for (int j = 0; j < 16; ++j) {
-      wr[0][j] = *reinterpret_cast<const float4*>(wb + 8 * j);
-      wr[1][j] = *reinterpret_cast<const float4*>(wb + (size_t)32 * C + 8 * j);
-    }
-  }
-  // register prefetch of the NEXT chunk
-  float4 pf[16];
-  auto prefetch = [&](int p0) __attribute__((always_inline)) {
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-      const int idx = (int)threadIdx.x + 256 * q;          // float4 index inside the chunk
-      const int i = p0 + (idx >> 7), c4 = (idx & 127) * 4;  // pixel of the quarter, channel
-      pf[q] = make_float4(0.f, 0.f, 0.f, 0.f);             // a pixel beyond the slab reads as zeros (a = 0 below)
-      if (i < p_hi) {
-        const int row = i / wq, col = i - row * wq;
-        pf[q] = *reinterpret_cast<const float4*>(fimg + ((size_t)row * wfull + col) * C + c4);
-      }
-    }
-  };
-  prefetch(p_lo);
-
-  for (int p0 = p_lo; p0 < p_hi; p0 += 32) {
-    // ---- the chunk -> LDS
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-      const int idx = (int)threadIdx.x + 256 * q;
-      *reinterpret_cast<float4*>(x_s + (idx >> 7) * RG_XP + (idx & 127) * 4) = pf[q];
-    }
-    __syncthreads();
-    if (p0 + 32 < p_hi) prefetch(p0 + 32);
-    // ---- 1 / |x_p|: eight threads per pixel, interleaved float4s
-    {
-      const int px = (int)threadIdx.x >> 3, sub = (int)threadIdx.x & 7;
-      float ss = 0.f;
-      if (normalize) {
-#pragma unroll
-        for (int j = 0; j < 16; ++j) {
-          const float4 v = *reinterpret_cast<const float4*>(x_s + px * RG_XP + 4 * (sub + 8 * j));
-          ss = fmaf(v.x, v.x, ss);
-          ss = fmaf(v.y, v.y, ss);
-          ss = fmaf(v.z, v.z, ss);
-          ss = fmaf(v.w, v.w, ss);
-        }
-        ss += __shfl_xor(ss, 1, 64);
-        ss += __shfl_xor(ss, 2, 64);
-        ss += __shfl_xor(ss, 4, 64);
-      }
-      if (sub == 0) inv_s[px] = normalize ? 1.0f / fmaxf(sqrtf(ss), 1e-12f) : 1.0f;
-    }
-    // ---- partial logits of this wave's 128 channels: [32 pixels] x [64 clusters]
-    {
-      f32x16_t lg[2];
-#pragma unroll
-      for (int ct = 0; ct < 2; ++ct)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) lg[ct][r] = 0.f;
-      const float* xa = x_s + l31 * RG_XP + 128 * wave + 4 * kh;
-#pragma unroll
-      for (int j = 0; j < 16; ++j) {
-        const float4 a = *reinterpret_cast<const float4*>(xa + 8 * j);
-        const float4 b0 = wr[0][j], b1 = wr[1][j];
-        lg[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b0.x, lg[0], 0, 0, 0);
-        lg[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b1.x, lg[1], 0, 0, 0);
-        lg[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, b0.y, lg[0], 0, 0, 0);
-        lg[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, b1.y, lg[1], 0, 0, 0);
-        lg[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, b0.z, lg[0], 0, 0, 0);
-        lg[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, b1.z, lg[1], 0, 0, 0);
-        lg[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, b0.w, lg[0], 0, 0, 0);
-        lg[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, b1.w, lg[1], 0, 0, 0);
-      }
-      float* lw = lp_s + wave * 32 * RG_LP;
-#pragma unroll
-      for (int ct = 0; ct < 2; ++ct)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) lw[acc_row(r, lane) * RG_LP + 32 * ct + l31] = lg[ct][r];
-    }
-    __syncthreads();
-    // ---- softmax over the 64 clusters: eight threads per pixel, eight clusters each
-    {
-      const int px = (int)threadIdx.x >> 3, sub = (int)threadIdx.x & 7;
-      const float iv = inv_s[px];
-      float l[8], mx = -INFINITY;
-#pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        const int o = px * RG_LP + sub * 8 + k;
-        l[k] = (lp_s[o] + lp_s[32 * RG_LP + o] + lp_s[2 * 32 * RG_LP + o] + lp_s[3 * 32 * RG_LP + o]) * iv;
-        mx = fmaxf(mx, l[k]);
-      }
-      mx = fmaxf(mx, __shfl_xor(mx, 1, 64));
-      mx = fmaxf(mx, __shfl_xor(mx, 2, 64));
-      mx = fmaxf(mx, __shfl_xor(mx, 4, 64));
-      float ssum = 0.f;
-#pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        l[k] = expf(l[k] - mx);
-        ssum += l[k];
-      }
-      ssum += __shfl_xor(ssum, 1, 64);
-      ssum += __shfl_xor(ssum, 2, 64);
-      ssum += __shfl_xor(ssum, 4, 64);
-      const float is = (p0 + px < p_hi) ? 1.0f / ssum : 0.f;
-#pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        const float a = l[k] * is;
-        a_s[px * RG_LP + sub * 8 + k] = a;
-        a2_s[px * RG_LP + sub * 8 + k] = a * iv;
-      }
-    }
-    __syncthreads();
-    if (threadIdx.x < 64) {
-#pragma unroll
-      for (int p = 0; p < 32; ++p) colsum += a_s[p * RG_LP + threadIdx.x];
-    }
-    // ---- aggregation: acc[k][c] += sum_p (a[p][k] / |x_p|) x[p][c]
-#pragma unroll 2
-    for (int s2 = 0; s2 < 16; ++s2) {
-      const int p = 2 * s2 + kh;
-      const float av0 = a2_s[p * RG_LP + l31], av1 = a2_s[p * RG_LP + 32 + l31];
-#pragma unroll
-      for (int ct = 0; ct < 4; ++ct) {
-        const float bv = x_s[p * RG_XP + 128 * wave + 32 * ct + l31];
-        acc[0][ct] = __builtin_amdgcn_mfma_f32_32x32x2f32(av0, bv, acc[0][ct], 0, 0, 0);
-        acc[1][ct] = __builtin_amdgcn_mfma_f32_32x32x2f32(av1, bv, acc[1][ct], 0, 0, 0);
-      }
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x < 64) cs_s[threadIdx.x] = colsum;
-  __syncthreads();
-  float* out = parts + (((size_t)n * 4 + quarter) * nslab + slab) * 64 * C;
-#pragma unroll
-  for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-    for (int ct = 0; ct < 4; ++ct) {
-      const int ch = 128 * wave + 32 * ct + l31;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int k = 32 * kt + acc_row(r, lane);
-        out[(size_t)k * C + ch] = acc[kt][ct][r] - cs_s[k] * centroids[(size_t)k * C + ch];
-      }
-    }
+  vlad_fused_slab(QuarterSlabs{hq, wq, nslab, slab_px}, feat, w, centroids, parts, normalize);
 }
 
 // One wave per (image, cluster) row; lane l holds channels 4 l .. 4 l + 3 and 256 + 4 l .. 256 + 4 l + 3 of the four
@@ -370,8 +186,8 @@ int oibl_region_vlad_forward(const void* feat, int N, int h, int w, int K, int C
   float* parts = (float*)ws;
   float* stats = (float*)((char*)ws + rg_off_stats(N, h, w, K, C));
   const int nslab = rg_nslab(h, w);
-  OIBL_SET_MAX_LDS(region_aggregate_kernel, RG_LDS);
-  hipLaunchKernelGGL(region_aggregate_kernel, dim3((unsigned)N, (unsigned)(4 * nslab)), dim3(256), RG_LDS, st,
+  OIBL_SET_MAX_LDS(region_aggregate_kernel, VLF_LDS);
+  hipLaunchKernelGGL(region_aggregate_kernel, dim3((unsigned)N, (unsigned)(4 * nslab)), dim3(256), VLF_LDS, st,
                      (const float*)feat, assign_w, centroids, parts, h / 2, w / 2, nslab, rg_slab_px(h, w),
                      normalize_input);
   OIBL_LAUNCH_CHECK();

@@ -83,7 +83,7 @@ __global__ __launch_bounds__(256) void rgb_aggregate_kernel(const float* __restr
 // st[(n 9 + r) K + k] = { |R_r,k| , |U_r,k|^2 , <U_r,k, G_r,k> }
 __global__ __launch_bounds__(256) void rgb_rowstats_kernel(const float* __restrict__ V, const float* __restrict__ G,
                                                            double* __restrict__ st, long rows) {
-  constexpr int C = VLB_C, K = VLB_K;
+  constexpr int C = VLAD_C, K = VLAD_K;
   const int lane = threadIdx.x & 63;
   const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
@@ -121,7 +121,7 @@ __global__ __launch_bounds__(256) void rgb_rowstats_kernel(const float* __restri
     for (int i = 0; i < 8; ++i) ss += rr[i] * rr[i];
     ss = wave_sum_f64(ss);
     const double t = sqrt(ss);
-    const double it = 1.0 / fmax(t, (double)VLB_EPS);
+    const double it = 1.0 / fmax(t, (double)VLAD_EPS);
     double s2 = 0.0, ug = 0.0;
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
@@ -150,7 +150,7 @@ __global__ __launch_bounds__(256) void rgb_dv_kernel(float* __restrict__ V, cons
                                                      const double* __restrict__ st, const double* __restrict__ A,
                                                      const float* __restrict__ centroids, float* __restrict__ dvc,
                                                      double* __restrict__ dCp, long rows) {
-  constexpr int C = VLB_C, K = VLB_K;
+  constexpr int C = VLAD_C, K = VLAD_K;
   const int lane = threadIdx.x & 63;
   const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
@@ -164,11 +164,11 @@ __global__ __launch_bounds__(256) void rgb_dv_kernel(float* __restrict__ V, cons
     const double S2 = wave_sum_f64(st[3 * (vbase + lane) + 1]);
     const double UG = wave_sum_f64(st[3 * (vbase + lane) + 2]);
     const double gn = sqrt(S2);
-    const double ig = 1.0 / fmax(gn, (double)VLB_EPS);
-    const double yg = gn < (double)VLB_EPS ? 0.0 : UG * ig;         // <Y_r, G_r>; a clamped g is a constant
+    const double ig = 1.0 / fmax(gn, (double)VLAD_EPS);
+    const double yg = gn < (double)VLAD_EPS ? 0.0 : UG * ig;         // <Y_r, G_r>; a clamped g is a constant
     const double t = st[3 * (vbase + k)], s2 = st[3 * (vbase + k) + 1], ug = st[3 * (vbase + k) + 2];
-    const double it = 1.0 / fmax(t, (double)VLB_EPS);
-    const double fd = t < (double)VLB_EPS ? 0.0 : (ug - s2 * ig * yg) * ig;   // <U_r,k, dU_r,k>; a clamped t likewise
+    const double it = 1.0 / fmax(t, (double)VLAD_EPS);
+    const double fd = t < (double)VLAD_EPS ? 0.0 : (ug - s2 * ig * yg) * ig;   // <U_r,k, dU_r,k>; a clamped t likewise
     al[r] = ig * it;
     be[r] = (ig * ig * yg + fd) * it * it;
   }
@@ -298,7 +298,7 @@ extern "C" {
 
 // workspace: vlad_backward_layout with P = h w, four units (the quarters) and nine normalised vectors per image
 static bool rgb_shape_ok(int N, int h, int w, int K, int C) {
-  return N > 0 && N <= 65535 && h >= 2 && w >= 2 && !(h & 1) && !(w & 1) && K == VLB_K && C == VLB_C &&
+  return N > 0 && N <= 65535 && h >= 2 && w >= 2 && !(h & 1) && !(w & 1) && K == VLAD_K && C == VLAD_C &&
          (long)h * w <= (1L << 22);            // chunks per quarter are a grid's y; N h w stays far below 2^31 rows
 }
 
@@ -316,7 +316,7 @@ int oibl_region_vlad_backward(const void* feat, int N, int h, int w, int K, int 
   OIBL_REQUIRE(grad_assign_w || grad_centroids || grad_feat, "region_vlad_backward: no output requested");
   OIBL_REQUIRE(precision == OIBL_F32, "region_vlad_backward: the feature map must be fp32 (OIBL_F32), got precision %d",
                precision);
-  OIBL_REQUIRE(K == VLB_K && C == VLB_C,
+  OIBL_REQUIRE(K == VLAD_K && C == VLAD_C,
                "region_vlad_backward: kernels are built for num_clusters = 64, dim = 512 (got %d, %d)", K, C);
   OIBL_REQUIRE(N > 0 && h > 0 && w > 0, "region_vlad_backward: bad shape N=%d h=%d w=%d", N, h, w);
   OIBL_REQUIRE(!(h & 1) && !(w & 1), "region_vlad_backward: the map is %d x %d, both sides must be even to cut quarters",
@@ -385,7 +385,7 @@ int oibl_region_vlad_backward(const void* feat, int N, int h, int w, int K, int 
     OIBL_LAUNCH_CHECK();
   }
   if (grad_assign_w || grad_centroids) {
-    hipLaunchKernelGGL(rgb_reduce_kernel, dim3(VLB_K * VLB_C / 256), dim3(256), 0, st, (const float*)dWp,
+    hipLaunchKernelGGL(rgb_reduce_kernel, dim3(VLAD_K * VLAD_C / 256), dim3(256), 0, st, (const float*)dWp,
                        (const double*)dCp, grad_assign_w, grad_centroids, N);
     OIBL_LAUNCH_CHECK();
   }

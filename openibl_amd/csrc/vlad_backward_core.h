@@ -29,21 +29,16 @@
 //   vlad_reduce        dW = sum_n dW_n (fp32), dC = sum_n dC_n (fp64, rounded once), both in image order
 #pragma once
 
-#include "gemm_core.h"
+#include "vlad_common.h"
 
 namespace oibl {
 
-constexpr int VLB_C = 512;
-constexpr int VLB_K = 64;
-constexpr int VLB_XP = 516;          // floats per LDS row of the chunk: 16-byte aligned, +4 banks per pixel
-constexpr int VLB_LP = 65;           // pitch of the [32][64] partial tiles
-constexpr int VLB_AP = 129;          // pitch of the [32][128] operand tile [a | ds]
+constexpr int VLB_AP = 129;         // pitch of the [32][128] operand tile [a | ds]
 constexpr int VLB_WP = 132;          // floats per LDS row of the weight slice: 16-byte aligned, +4 banks per cluster
 // dynamic LDS of the three chunk kernels without the map's table: a launch asks for these + Map::TABLE_BYTES
-constexpr int VLB_ASSIGN_LDS = (32 * VLB_XP + VLB_K * VLB_WP) * 4;
-constexpr int VLB_CONTRACT_LDS = (32 * VLB_XP + 4 * 32 * VLB_LP + 32) * 4;
-constexpr int VLB_DX_LDS = (32 * VLB_XP + 32 * VLB_AP + 4 * 32 + 32 + 32) * 4;
-constexpr float VLB_EPS = 1e-12f;
+constexpr int VLB_ASSIGN_LDS = (32 * VLAD_XP + VLAD_K * VLB_WP) * 4;
+constexpr int VLB_CONTRACT_LDS = (32 * VLAD_XP + 4 * 32 * VLAD_LP + 32) * 4;
+constexpr int VLB_DX_LDS = (32 * VLAD_XP + 32 * VLB_AP + 4 * 32 + 32 + 32) * 4;
 
 __device__ static inline double wave_sum_f64(double v) {
 #pragma unroll
@@ -75,11 +70,7 @@ struct QuarterMap {
   __device__ int pixels() const { return hq * wq; }
   __device__ int image_pixels() const { return 4 * hq * wq; }
   __device__ size_t image_row(int m) const { return (size_t)(m >> 2) * 4 * (hq * wq); }
-  // the map pixel (row-major in the h x w map) of pixel i of quarter q
-  __device__ int map_pixel(int q, int i) const {
-    const int row = i / wq, col = i - row * wq;
-    return ((q >> 1) * hq + row) * (2 * wq) + (q & 1) * wq + col;
-  }
+  __device__ int map_pixel(int q, int i) const { return quarter_map_pixel(q, i, hq, wq); }
   // tab[t] = map pixel of pixel p0 + t of unit m, -1 beyond the unit (threads 0..31), then the barrier that
   // publishes it
   __device__ void prepare(int m, int p0, int* tab) const {
@@ -97,7 +88,7 @@ struct QuarterMap {
   }
 };
 
-// the chunk [p0, p0 + 32) of one unit -> x_s[32][VLB_XP]; pixels beyond the unit read as zeros
+// the chunk [p0, p0 + 32) of one unit -> x_s[32][VLAD_XP]; pixels beyond the unit read as zeros
 template <class Map>
 __device__ __forceinline__ void vlad_load_chunk(const Map map, const float* __restrict__ fimg, int p0, const int* tab,
                                                 float* x_s) {
@@ -107,8 +98,8 @@ __device__ __forceinline__ void vlad_load_chunk(const Map map, const float* __re
     const int px = idx >> 7, c4 = (idx & 127) * 4;
     float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
     if (map.live(p0, px, tab))
-      v = *reinterpret_cast<const float4*>(fimg + (size_t)map.pixel(p0, px, tab) * VLB_C + c4);
-    *reinterpret_cast<float4*>(x_s + px * VLB_XP + c4) = v;
+      v = *reinterpret_cast<const float4*>(fimg + (size_t)map.pixel(p0, px, tab) * VLAD_C + c4);
+    *reinterpret_cast<float4*>(x_s + px * VLAD_XP + c4) = v;
   }
 }
 
@@ -123,10 +114,10 @@ __device__ __forceinline__ void vlad_load_chunk(const Map map, const float* __re
 template <class Map>
 __device__ __forceinline__ void vlad_assign(const Map map, const float* __restrict__ feat, const float* __restrict__ w,
                                             float* __restrict__ rn, float* __restrict__ a, int normalize) {
-  constexpr int C = VLB_C;
+  constexpr int C = VLAD_C;
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* const x_s = reinterpret_cast<float*>(smem);             // [32][VLB_XP]
-  float* const w_s = x_s + 32 * VLB_XP;                           // [64 clusters][VLB_WP]: 128 channels of a slice
+  float* const x_s = reinterpret_cast<float*>(smem);             // [32][VLAD_XP]
+  float* const w_s = x_s + 32 * VLAD_XP;                           // [64 clusters][VLB_WP]: 128 channels of a slice
   int* const tab = reinterpret_cast<int*>(smem + VLB_ASSIGN_LDS);  // the map's table
   const int Pu = map.pixels();
   const int m = map.unit(), p0 = map.chunk() * 32;
@@ -146,7 +137,7 @@ __device__ __forceinline__ void vlad_assign(const Map map, const float* __restri
           *reinterpret_cast<const float4*>(w + (size_t)k * C + c0 + 4 * c4);
     }
     __syncthreads();
-    const float* xr = x_s + px * VLB_XP + c0;
+    const float* xr = x_s + px * VLAD_XP + c0;
     const float* wr = w_s + sub * VLB_WP;
 #pragma unroll 2
     for (int c = 0; c < 128; c += 4) {
@@ -167,7 +158,7 @@ __device__ __forceinline__ void vlad_assign(const Map map, const float* __restri
     }
   }
   const double rd = normalize ? sqrt(ss) : 1.0;
-  const double invd = 1.0 / fmax(rd, (double)VLB_EPS);
+  const double invd = 1.0 / fmax(rd, (double)VLAD_EPS);
   float l[8], mx = -INFINITY;
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
@@ -189,7 +180,7 @@ __device__ __forceinline__ void vlad_assign(const Map map, const float* __restri
   const float is = 1.0f / ssum;
   if (p0 + px < Pu) {
     const size_t row = (size_t)m * Pu + p0 + px;
-    float* dst = a + row * VLB_K + sub;
+    float* dst = a + row * VLAD_K + sub;
 #pragma unroll
     for (int j = 0; j < 8; ++j) dst[8 * j] = l[j] * is;         // the eight threads of a pixel: 32 bytes per j
     if (sub == 0) rn[row] = (float)rd;
@@ -204,24 +195,24 @@ template <class Map>
 __device__ __forceinline__ void vlad_contract(const Map map, const float* __restrict__ feat,
                                               const float* __restrict__ B, const float* __restrict__ dvc,
                                               const float* __restrict__ rn, const float* a, float* out) {
-  constexpr int C = VLB_C;
+  constexpr int C = VLAD_C;
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* const x_s = reinterpret_cast<float*>(smem);             // [32][VLB_XP]
-  float* const lp_s = x_s + 32 * VLB_XP;                          // [4 waves][32][VLB_LP]
-  float* const inv_s = lp_s + 4 * 32 * VLB_LP;                    // [32]
+  float* const x_s = reinterpret_cast<float*>(smem);             // [32][VLAD_XP]
+  float* const lp_s = x_s + 32 * VLAD_XP;                          // [4 waves][32][VLAD_LP]
+  float* const inv_s = lp_s + 4 * 32 * VLAD_LP;                    // [32]
   int* const tab = reinterpret_cast<int*>(smem + VLB_CONTRACT_LDS);  // the map's table
   const int Pu = map.pixels();
   const int m = map.unit(), p0 = map.chunk() * 32;
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int l31 = lane & 31, kh = lane >> 5;
-  B += (size_t)m * VLB_K * C;
+  B += (size_t)m * VLAD_K * C;
 
   map.prepare(m, p0, tab);
   vlad_load_chunk(map, feat + map.image_row(m) * C, p0, tab, x_s);
   if (threadIdx.x < 32) {
     const int p = p0 + (int)threadIdx.x;
-    inv_s[threadIdx.x] = p < Pu ? 1.0f / fmaxf(rn[(size_t)m * Pu + p], VLB_EPS) : 0.f;
+    inv_s[threadIdx.x] = p < Pu ? 1.0f / fmaxf(rn[(size_t)m * Pu + p], VLAD_EPS) : 0.f;
   }
   __syncthreads();
   {  // partial contraction over this wave's 128 channels: [32 pixels] x [64 rows of B]
@@ -230,7 +221,7 @@ __device__ __forceinline__ void vlad_contract(const Map map, const float* __rest
     for (int ct = 0; ct < 2; ++ct)
 #pragma unroll
       for (int r = 0; r < 16; ++r) lg[ct][r] = 0.f;
-    const float* xa = x_s + l31 * VLB_XP + 128 * wave + 4 * kh;
+    const float* xa = x_s + l31 * VLAD_XP + 128 * wave + 4 * kh;
     const float* wb = B + (size_t)l31 * C + 128 * wave + 4 * kh;
 #pragma unroll 4
     for (int j = 0; j < 16; ++j) {
@@ -246,11 +237,11 @@ __device__ __forceinline__ void vlad_contract(const Map map, const float* __rest
       lg[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, b0.w, lg[0], 0, 0, 0);
       lg[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, b1.w, lg[1], 0, 0, 0);
     }
-    float* lw = lp_s + wave * 32 * VLB_LP;
+    float* lw = lp_s + wave * 32 * VLAD_LP;
 #pragma unroll
     for (int ct = 0; ct < 2; ++ct)
 #pragma unroll
-      for (int r = 0; r < 16; ++r) lw[acc_row(r, lane) * VLB_LP + 32 * ct + l31] = lg[ct][r];
+      for (int r = 0; r < 16; ++r) lw[acc_row(r, lane) * VLAD_LP + 32 * ct + l31] = lg[ct][r];
   }
   __syncthreads();
   {  // eight threads per pixel, eight clusters each
@@ -260,10 +251,10 @@ __device__ __forceinline__ void vlad_contract(const Map map, const float* __rest
     float l[8];
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
-      const int o = px * VLB_LP + sub * 8 + k;
-      l[k] = (lp_s[o] + lp_s[32 * VLB_LP + o] + lp_s[2 * 32 * VLB_LP + o] + lp_s[3 * 32 * VLB_LP + o]) * iv;
+      const int o = px * VLAD_LP + sub * 8 + k;
+      l[k] = (lp_s[o] + lp_s[32 * VLAD_LP + o] + lp_s[2 * 32 * VLAD_LP + o] + lp_s[3 * 32 * VLAD_LP + o]) * iv;
     }
-    const size_t off = ((size_t)m * Pu + p0 + px) * VLB_K + sub * 8;
+    const size_t off = ((size_t)m * Pu + p0 + px) * VLAD_K + sub * 8;
     float av[8];
 #pragma unroll
     for (int k = 0; k < 8; ++k) av[k] = 0.f;
@@ -275,7 +266,7 @@ __device__ __forceinline__ void vlad_contract(const Map map, const float* __rest
     float dot = 0.f;
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
-      l[k] -= dvc[m * VLB_K + sub * 8 + k];
+      l[k] -= dvc[m * VLAD_K + sub * 8 + k];
       dot = fmaf(av[k], l[k], dot);
     }
     dot += __shfl_xor(dot, 1, 64);
@@ -300,7 +291,7 @@ __device__ __forceinline__ void vlad_aggregate(const Map map, const float* __res
                                                const float* __restrict__ rn, const float* __restrict__ a,
                                                const float* __restrict__ centroids, float* __restrict__ out,
                                                double* __restrict__ A, int segs, int seg_px) {
-  constexpr int C = VLB_C;
+  constexpr int C = VLAD_C;
   __shared__ __attribute__((aligned(16))) float a_s[32][64];
   __shared__ __attribute__((aligned(16))) float x_s[32][64];
   __shared__ float s_sum[64];
@@ -336,7 +327,7 @@ __device__ __forceinline__ void vlad_aggregate(const Map map, const float* __res
     px1 = px0;
     psc = 0.f;
     if (p0 + xp < seg_px) {
-      psc = 1.0f / fmaxf(rbase[p0 + xp], VLB_EPS);
+      psc = 1.0f / fmaxf(rbase[p0 + xp], VLAD_EPS);
       const float* src = fbase + (size_t)map.image_pixel(j0 + p0 + xp) * C + xc;
       px0 = *reinterpret_cast<const float4*>(src);
       px1 = *reinterpret_cast<const float4*>(src + 4);
@@ -391,10 +382,10 @@ __device__ __forceinline__ void vlad_dx(const Map map, const float* __restrict__
                                         const float* __restrict__ a, const float* __restrict__ ds,
                                         const float* __restrict__ dV, const float* __restrict__ w,
                                         float* __restrict__ grad_feat, int normalize) {
-  constexpr int C = VLB_C;
+  constexpr int C = VLAD_C;
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* const x_s = reinterpret_cast<float*>(smem);             // [32][VLB_XP]
-  float* const ad_s = x_s + 32 * VLB_XP;                          // [32][VLB_AP]: a | ds
+  float* const x_s = reinterpret_cast<float*>(smem);             // [32][VLAD_XP]
+  float* const ad_s = x_s + 32 * VLAD_XP;                          // [32][VLB_AP]: a | ds
   float* const red_s = ad_s + 32 * VLB_AP;                        // [4 waves][32]
   float* const inv_s = red_s + 4 * 32;                            // [32]
   float* const dot_s = inv_s + 32;                                // [32]
@@ -405,7 +396,7 @@ __device__ __forceinline__ void vlad_dx(const Map map, const float* __restrict__
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int l31 = lane & 31, kh = lane >> 5;
   const size_t row0 = (size_t)m * Pu;                             // the unit's first workspace row
-  dV += (size_t)m * VLB_K * C;
+  dV += (size_t)m * VLAD_K * C;
 
   map.prepare(m, p0, tab);
   vlad_load_chunk(map, feat + map.image_row(m) * C, p0, tab, x_s);
@@ -415,7 +406,7 @@ __device__ __forceinline__ void vlad_dx(const Map map, const float* __restrict__
     const int px = idx >> 5, k4 = (idx & 31) * 4;                 // k4 < 64: a, else ds
     float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
     if (p0 + px < Pu) {
-      const float* src = (k4 < 64 ? a : ds) + (row0 + p0 + px) * VLB_K + (k4 & 63);
+      const float* src = (k4 < 64 ? a : ds) + (row0 + p0 + px) * VLAD_K + (k4 & 63);
       v = *reinterpret_cast<const float4*>(src);
     }
     float* d = ad_s + px * VLB_AP + k4;
@@ -423,7 +414,7 @@ __device__ __forceinline__ void vlad_dx(const Map map, const float* __restrict__
   }
   if (threadIdx.x < 32) {
     const int p = p0 + (int)threadIdx.x;
-    inv_s[threadIdx.x] = p < Pu ? 1.0f / fmaxf(rn[row0 + p], VLB_EPS) : 0.f;
+    inv_s[threadIdx.x] = p < Pu ? 1.0f / fmaxf(rn[row0 + p], VLAD_EPS) : 0.f;
     // the projection is dropped where the input is not normalised or its norm sits on the clamp
     dot_s[threadIdx.x] = 0.f;
   }
@@ -456,7 +447,7 @@ __device__ __forceinline__ void vlad_dx(const Map map, const float* __restrict__
       const int px = acc_row(r, lane);
       float v = 0.f;
 #pragma unroll
-      for (int ct = 0; ct < 4; ++ct) v = fmaf(acc[ct][r], x_s[px * VLB_XP + cb + 32 * ct], v);
+      for (int ct = 0; ct < 4; ++ct) v = fmaf(acc[ct][r], x_s[px * VLAD_XP + cb + 32 * ct], v);
       v += __shfl_xor(v, 16, 64);
       v += __shfl_xor(v, 8, 64);
       v += __shfl_xor(v, 4, 64);
@@ -468,7 +459,7 @@ __device__ __forceinline__ void vlad_dx(const Map map, const float* __restrict__
     if (threadIdx.x < 32) {
       const int p = p0 + (int)threadIdx.x;
       const float iv = inv_s[threadIdx.x];
-      const bool clamped = p < Pu ? rn[row0 + p] < VLB_EPS : true;
+      const bool clamped = p < Pu ? rn[row0 + p] < VLAD_EPS : true;
       const float d = ((red_s[threadIdx.x] + red_s[32 + threadIdx.x]) + red_s[64 + threadIdx.x]) + red_s[96 + threadIdx.x];
       dot_s[threadIdx.x] = clamped ? 0.f : d * iv * iv;         // <xh_p, dxh_p> / r_p: it multiplies x_p below
     }
@@ -484,7 +475,7 @@ __device__ __forceinline__ void vlad_dx(const Map map, const float* __restrict__
 #pragma unroll
       for (int ct = 0; ct < 4; ++ct) {
         const int ch = cb + 32 * ct;
-        gimg[mp * C + ch] = (acc[ct][r] - x_s[px * VLB_XP + ch] * d) * iv;
+        gimg[mp * C + ch] = (acc[ct][r] - x_s[px * VLAD_XP + ch] * d) * iv;
       }
     }
   }
@@ -493,7 +484,7 @@ __device__ __forceinline__ void vlad_dx(const Map map, const float* __restrict__
 // dW = sum_n dWp[n] (fp32), dC = sum_n dCp[n] (fp64, rounded once), both in image order; either output may be null
 __device__ __forceinline__ void vlad_reduce(const float* __restrict__ dWp, const double* __restrict__ dCp,
                                             float* __restrict__ dW, float* __restrict__ dC, int N) {
-  constexpr int KC = VLB_K * VLB_C;
+  constexpr int KC = VLAD_K * VLAD_C;
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= KC) return;
   if (dW) {
@@ -518,7 +509,7 @@ struct VladBackwardLayout {
 };
 static inline VladBackwardLayout vlad_backward_layout(size_t N, size_t P, size_t units, size_t stat_rows,
                                                       int want_grad_feat) {
-  constexpr size_t K = VLB_K, C = VLB_C;
+  constexpr size_t K = VLAD_K, C = VLAD_C;
   VladBackwardLayout o;
   o.a = align_up(N * P * sizeof(float), 256);
   o.v = o.a + align_up(N * P * 64 * sizeof(float), 256);

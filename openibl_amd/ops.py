@@ -495,6 +495,63 @@ def nchw_f32_to_nhwc(x: torch.Tensor, precision) -> torch.Tensor:
 
 
 # ---- NetVLAD ----------------------------------------------------------------------------------
+# argument checks the two heads' wrappers share; `what` is the caller's name, as in _tuple_rows
+def _head_weights(what: str, assign_w: torch.Tensor, centroids: torch.Tensor, C_: int, dense_centroids: bool = False):
+    """(K, assign_w as a contiguous float32 [K][C] view); the region head also wants its centroids contiguous."""
+    K = int(centroids.shape[0])
+    aw = assign_w.reshape(K, C_)
+    if aw.dtype != torch.float32 or centroids.dtype != torch.float32 or not aw.is_contiguous() \
+            or (dense_centroids and not centroids.is_contiguous()):
+        raise ValueError(f"{what}: assign_w / centroids must be contiguous float32")
+    return K, aw
+
+
+def _want_letters(what: str, want: Sequence[str]) -> Tuple[str, ...]:
+    want = tuple(want)
+    if not want or any(t not in ("w", "c", "x") for t in want):
+        raise ValueError(f"{what}: want must name some of 'w', 'c', 'x' (got {want!r})")
+    return want
+
+
+def _even_sides(what: str, h: int, w: int) -> None:
+    if h % 2 or w % 2 or h == 0 or w == 0:
+        raise ValueError(f"{what}: the conv5 map is {h} x {w}, both sides must be even to cut it into quarters")
+
+
+def _region_tuples(what: str, region_vlad: torch.Tensor, tuple_size: int, tensor_msg: str):
+    """Validate region vectors [N][9][L] against tuple_size and return (N, L, T)."""
+    if region_vlad.dim() != 3 or int(region_vlad.shape[1]) != 9 or region_vlad.dtype != torch.float32 \
+            or not region_vlad.is_contiguous():
+        raise ValueError(f"{what}: {tensor_msg}")
+    N, _, L = map(int, region_vlad.shape)
+    T = int(tuple_size)
+    if T <= 0 or N % T:
+        raise ValueError(f"{what}: {N} images are not a multiple of tuple_size {T}")
+    if N // T < 2:
+        raise ValueError(f"{what}: a tuple needs an anchor and at least one pair (got {N // T} image per tuple)")
+    return N, L, T
+
+
+# what the two heads' autograd Functions share (each names its own pair of functions where it calls them)
+def _head_forward(ctx, head, feat, assign_w, centroids, normalize_input):
+    ctx.save_for_backward(feat, assign_w, centroids)
+    ctx.normalize_input = bool(normalize_input)
+    return head(feat, assign_w, centroids, normalize_input=ctx.normalize_input)
+
+
+def _head_backward(ctx, head_backward, grad_out):
+    """One call of `head_backward` for exactly the inputs that need a gradient."""
+    feat, assign_w, centroids = ctx.saved_tensors
+    want = tuple(t for t, n in zip(("x", "w", "c"), ctx.needs_input_grad[:3]) if n)
+    if not want:
+        return None, None, None, None
+    gw, gc, gx = head_backward(feat, assign_w, centroids, grad_out.contiguous(),
+                               normalize_input=ctx.normalize_input, want=want)
+    if gw is not None:
+        gw = gw.reshape(assign_w.shape)
+    return gx, gw, gc, None
+
+
 def netvlad(feat: torch.Tensor, assign_w: torch.Tensor, centroids: torch.Tensor,
             normalize_input: bool = True, want_raw: bool = False, want_norm: bool = True):
     """feat [N][h][w][C] (or [N][P][C]) T -> (vlad_raw [N][K][C] | None, vlad_norm [N][K*C] | None)."""
@@ -504,10 +561,7 @@ def netvlad(feat: torch.Tensor, assign_w: torch.Tensor, centroids: torch.Tensor,
         raise ValueError("netvlad: feature map must be bf16 or fp32")
     N, C_ = int(feat.shape[0]), int(feat.shape[-1])
     P = feat.numel() // (N * C_)
-    K = int(centroids.shape[0])
-    aw = assign_w.reshape(K, C_)
-    if aw.dtype != torch.float32 or centroids.dtype != torch.float32 or not aw.is_contiguous():
-        raise ValueError("netvlad: assign_w / centroids must be contiguous float32")
+    K, aw = _head_weights("netvlad", assign_w, centroids, C_)
     lib = _lib.load()
     ws_bytes = lib.oibl_netvlad_workspace_bytes(N, P, K, C_)
     ws = workspace(ws_bytes, dev, "netvlad")
@@ -527,17 +581,12 @@ def netvlad_backward(feat: torch.Tensor, assign_w: torch.Tensor, centroids: torc
     feat | None) for the letters in `want` ("w", "c", "x").  Stateless: the forward's intermediates are recomputed
     from feat.  Bit-identical from run to run; an output does not depend on which others are asked for."""
     dev = _need_cuda(feat, assign_w, centroids, grad_out)
-    want = tuple(want)
-    if not want or any(t not in ("w", "c", "x") for t in want):
-        raise ValueError(f"netvlad_backward: want must name some of 'w', 'c', 'x' (got {want!r})")
+    want = _want_letters("netvlad_backward", want)
     if feat.dtype != torch.float32 or grad_out.dtype != torch.float32:
         raise ValueError("netvlad_backward: feature map and grad_out must be fp32")
     N, C_ = int(feat.shape[0]), int(feat.shape[-1])
     P = feat.numel() // (N * C_)
-    K = int(centroids.shape[0])
-    aw = assign_w.reshape(K, C_)
-    if aw.dtype != torch.float32 or centroids.dtype != torch.float32 or not aw.is_contiguous():
-        raise ValueError("netvlad_backward: assign_w / centroids must be contiguous float32")
+    K, aw = _head_weights("netvlad_backward", assign_w, centroids, C_)
     if grad_out.numel() != N * K * C_:
         raise ValueError(f"netvlad_backward: grad_out has {grad_out.numel()} elements, expected {N} x {K * C_}")
     lib = _lib.load()
@@ -553,23 +602,12 @@ def netvlad_backward(feat: torch.Tensor, assign_w: torch.Tensor, centroids: torc
 
 class _NetVLADHead(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, feat, assign_w, centroids, normalize_input):
-        ctx.save_for_backward(feat, assign_w, centroids)
-        ctx.normalize_input = bool(normalize_input)
-        return netvlad(feat, assign_w, centroids, normalize_input=ctx.normalize_input, want_norm=True)[1]
+    def forward(ctx, *args):
+        return _head_forward(ctx, netvlad, *args)[1]
 
     @staticmethod
     def backward(ctx, grad_out):
-        feat, assign_w, centroids = ctx.saved_tensors
-        need = ctx.needs_input_grad
-        want = tuple(t for t, n in zip(("x", "w", "c"), need[:3]) if n)
-        if not want:
-            return None, None, None, None
-        gw, gc, gx = netvlad_backward(feat, assign_w, centroids, grad_out.contiguous(),
-                                      normalize_input=ctx.normalize_input, want=want)
-        if gw is not None:
-            gw = gw.reshape(assign_w.shape)
-        return gx, gw, gc, None
+        return _head_backward(ctx, netvlad_backward, grad_out)
 
 
 def netvlad_head(feat: torch.Tensor, assign_w: torch.Tensor, centroids: torch.Tensor,
@@ -659,14 +697,9 @@ def region_vlad(feat: torch.Tensor, assign_w: torch.Tensor, centroids: torch.Ten
     if feat.dim() != 4 or feat.dtype not in (torch.bfloat16, torch.float32):
         raise ValueError("region_vlad: feature map must be a bf16 or fp32 [N][h][w][C] tensor")
     N, h, w, C_ = map(int, feat.shape)
-    if h % 2 or w % 2 or h == 0 or w == 0:
-        raise ValueError(f"region_vlad: the conv5 map is {h} x {w}, both sides must be even to cut it into quarters")
+    _even_sides("region_vlad", h, w)
     feat = feat.float().contiguous()
-    K = int(centroids.shape[0])
-    aw = assign_w.reshape(K, C_)
-    if aw.dtype != torch.float32 or centroids.dtype != torch.float32 or not aw.is_contiguous() \
-            or not centroids.is_contiguous():
-        raise ValueError("region_vlad: assign_w / centroids must be contiguous float32")
+    K, aw = _head_weights("region_vlad", assign_w, centroids, C_, dense_centroids=True)
     lib = _lib.load()
     ws = workspace(lib.oibl_region_workspace_bytes(N, h, w, K, C_), dev, "region")
     out = torch.empty((N, 9, K * C_), dtype=torch.float32, device=dev)
@@ -680,15 +713,7 @@ def region_scores(region_vlad: torch.Tensor, tuple_size: int) -> torch.Tensor:
     """region_vlad [T*(1+n)][9][L] fp32, tuple-major with the anchor first -> score [T][n][9][9],
     score[t, j, a, b] = <region a of tuple t's anchor, region b of its pair j> (netvlad.py:177-184)."""
     dev = _need_cuda(region_vlad)
-    if region_vlad.dim() != 3 or int(region_vlad.shape[1]) != 9 or region_vlad.dtype != torch.float32 \
-            or not region_vlad.is_contiguous():
-        raise ValueError("region_scores: a contiguous float32 [N][9][L] tensor")
-    N, _, L = map(int, region_vlad.shape)
-    T = int(tuple_size)
-    if T <= 0 or N % T:
-        raise ValueError(f"region_scores: {N} images are not a multiple of tuple_size {T}")
-    if N // T < 2:
-        raise ValueError(f"region_scores: a tuple needs an anchor and at least one pair (got {N // T} image per tuple)")
+    N, L, T = _region_tuples("region_scores", region_vlad, tuple_size, "a contiguous float32 [N][9][L] tensor")
     score = torch.empty((T, N // T - 1, 9, 9), dtype=torch.float32, device=dev)
     _lib.check(_lib.load().oibl_region_scores(_ptr(region_vlad), T, N // T, L, _ptr(score), _stream(dev)),
                "region_scores")
@@ -702,22 +727,14 @@ def region_vlad_backward(feat: torch.Tensor, assign_w: torch.Tensor, centroids: 
     feat | None) for the letters in `want` ("w", "c", "x").  Stateless: the forward's intermediates are recomputed
     from feat.  Bit-identical from run to run; an output does not depend on which others are asked for."""
     dev = _need_cuda(feat, assign_w, centroids, grad_out)
-    want = tuple(want)
-    if not want or any(t not in ("w", "c", "x") for t in want):
-        raise ValueError(f"region_vlad_backward: want must name some of 'w', 'c', 'x' (got {want!r})")
+    want = _want_letters("region_vlad_backward", want)
     if feat.dim() != 4 or feat.dtype != torch.float32 or grad_out.dtype != torch.float32:
         raise ValueError("region_vlad_backward: feature map [N][h][w][C] and grad_out must be fp32")
     if not feat.is_contiguous() or not grad_out.is_contiguous():
         raise ValueError("region_vlad_backward: feature map and grad_out must be contiguous")
     N, h, w, C_ = map(int, feat.shape)
-    if h % 2 or w % 2 or h == 0 or w == 0:
-        raise ValueError(f"region_vlad_backward: the conv5 map is {h} x {w}, both sides must be even to cut it into "
-                         f"quarters")
-    K = int(centroids.shape[0])
-    aw = assign_w.reshape(K, C_)
-    if aw.dtype != torch.float32 or centroids.dtype != torch.float32 or not aw.is_contiguous() \
-            or not centroids.is_contiguous():
-        raise ValueError("region_vlad_backward: assign_w / centroids must be contiguous float32")
+    _even_sides("region_vlad_backward", h, w)
+    K, aw = _head_weights("region_vlad_backward", assign_w, centroids, C_, dense_centroids=True)
     if grad_out.numel() != N * 9 * K * C_:
         raise ValueError(f"region_vlad_backward: grad_out has {grad_out.numel()} elements, expected {N} x 9 x {K * C_}")
     lib = _lib.load()
@@ -735,16 +752,8 @@ def region_scores_backward(region_vlad: torch.Tensor, grad_score: torch.Tensor, 
     """Gradient of `region_scores(region_vlad, tuple_size)` (oibl_region_scores_backward): region_vlad
     [T*(1+n)][9][L] fp32 as given to the forward, grad_score [T][n][9][9] fp32 -> dL/d region_vlad, same shape."""
     dev = _need_cuda(region_vlad, grad_score)
-    if region_vlad.dim() != 3 or int(region_vlad.shape[1]) != 9 or region_vlad.dtype != torch.float32 \
-            or not region_vlad.is_contiguous():
-        raise ValueError("region_scores_backward: region_vlad must be a contiguous float32 [N][9][L] tensor")
-    N, _, L = map(int, region_vlad.shape)
-    T = int(tuple_size)
-    if T <= 0 or N % T:
-        raise ValueError(f"region_scores_backward: {N} images are not a multiple of tuple_size {T}")
-    if N // T < 2:
-        raise ValueError(f"region_scores_backward: a tuple needs an anchor and at least one pair (got {N // T} image "
-                         f"per tuple)")
+    N, L, T = _region_tuples("region_scores_backward", region_vlad, tuple_size,
+                             "region_vlad must be a contiguous float32 [N][9][L] tensor")
     if grad_score.dtype != torch.float32 or not grad_score.is_contiguous() \
             or tuple(grad_score.shape) != (T, N // T - 1, 9, 9):
         raise ValueError(f"region_scores_backward: grad_score must be a contiguous float32 [{T}][{N // T - 1}][9][9]")
@@ -756,22 +765,12 @@ def region_scores_backward(region_vlad: torch.Tensor, grad_score: torch.Tensor, 
 
 class _RegionVLAD(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, feat, assign_w, centroids, normalize_input):
-        ctx.save_for_backward(feat, assign_w, centroids)
-        ctx.normalize_input = bool(normalize_input)
-        return region_vlad(feat, assign_w, centroids, normalize_input=ctx.normalize_input)
+    def forward(ctx, *args):
+        return _head_forward(ctx, region_vlad, *args)
 
     @staticmethod
     def backward(ctx, grad_out):
-        feat, assign_w, centroids = ctx.saved_tensors
-        want = tuple(t for t, n in zip(("x", "w", "c"), ctx.needs_input_grad[:3]) if n)
-        if not want:
-            return None, None, None, None
-        gw, gc, gx = region_vlad_backward(feat, assign_w, centroids, grad_out.contiguous(),
-                                          normalize_input=ctx.normalize_input, want=want)
-        if gw is not None:
-            gw = gw.reshape(assign_w.shape)
-        return gx, gw, gc, None
+        return _head_backward(ctx, region_vlad_backward, grad_out)
 
 
 class _RegionScores(torch.autograd.Function):

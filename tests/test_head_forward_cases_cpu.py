@@ -41,7 +41,10 @@ def test_restated_constants_are_the_sources():
     assert "return N >= 16 ? 160 : N >= 8 ? 96 : N >= 4 ? 64 : 32;" in nv
     assert "(((P + slabs - 1) / slabs + 31) / 32) * 32" in nv
     assert "Cfg::BN == 64 && Cfg::BM == 128" in nv and hf.ASSIGN_BM == 128
-    assert "p0 += 32" in nv and "p0 += 32" in rg and hf.CHUNK == 32
+    core = _src("vlad_forward_core.h")                                # the slab body both units wrap
+    assert '#include "vlad_forward_core.h"' in nv and '#include "vlad_forward_core.h"' in rg
+    assert "vlad_fused_slab(PlainSlabs{" in nv and "vlad_fused_slab(QuarterSlabs{" in rg
+    assert "p0 += 32" in nv and "p0 += 32" in core and hf.CHUNK == 32
     assert _const(rg, "RG_SLAB_TARGET") == hf.RG_SLAB_TARGET
     for name in ("PS_ROWS", "PS_SPLITS", "PS_MAXN", "PK_WAVES", "PK_SPLITS", "PK_CHUNK", "PK_MAXN", "PRN_PER"):
         assert _const(pca, name) == getattr(hf, name), name
