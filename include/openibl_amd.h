@@ -636,6 +636,37 @@ size_t oibl_row_argsort_workspace_bytes(int m, int n);
 int oibl_row_argsort(const float* vals, int m, int n, size_t ld, int32_t* out_idx, float* out_val,
                      void* ws, size_t ws_bytes, void* stream);
 
+/* ---- hard-negative mining, per anchor row ---------------------------------------------- *
+ * Replaces the per-anchor bookkeeping of the tuple samplers' __iter__ (ibl/utils/data/sampler.py:62-86,
+ * 143-190: the membership tests over the whole ranked row) for the A anchors of one mining round.
+ *   dist [A][ld] fp32        the anchors' distance rows over G gallery items.  "Rank order" of a row is
+ *                            ascending (distance, gallery index): the order of oibl_row_argsort, which ranks
+ *                            the rows inside this entry (bit patterns: -0.0 sorts before +0.0).
+ *   csr_row [A] int32        the row of the two CSR lists that belongs to anchor a; NULL: row a.
+ *   pos_off / pos_val        CSR, int32: the anchor's positives; every row ascending, without repeats, inside
+ *   excl_off / excl_val      [0, G) (np.unique of the sampler's pos_list / neg_list entry); the exclusion zone.
+ *                            The caller guarantees offsets and rows (they live on the device).
+ *   cache [A][C] int32       last round's negatives, -1 = none; C <= 64 (C = 0: cache, cache_pos may be NULL).
+ *   jac [A][jac_ld] fp32     the k-reciprocal distances of the same rows, or NULL.
+ * Per anchor:
+ *   cand [A][cand_ld]        the row in rank order without the excluded entries, -1 behind cand_len[a];
+ *                            cand_ld >= G.
+ *   cand_len [A]
+ *   cache_pos [A][C]         the position in cand of cache[a][c]; -1 for a -1 entry and for an excluded one.
+ *   pos_ranked [A][pos_pool] the anchor's positives in rank order, the first pos_pool of them, -1 behind;
+ *                            column 0 is the easiest positive.  1 <= pos_pool <= 1024.
+ *   pos_jac [A][pos_pool]    jac[a][pos_ranked[a][j]], NaN where pos_ranked is -1; untouched when jac is NULL.
+ * One pass over the ranked row per anchor; exclusion lists of up to 4096 entries are searched in LDS, longer
+ * ones in global memory.  Integer results and copied floats only, no atomics: identical bits from run to run.
+ * The workspace holds the ranking and the sort's buffers: 20 bytes per element of dist; a caller bounds it by
+ * mining the rows in groups (every pointer advanced by the rows done; csr_row or the offsets likewise). */
+size_t oibl_mine_rows_workspace_bytes(int A, int G);
+int oibl_mine_rows(const float* dist, int A, int G, size_t ld, const int32_t* csr_row, const int32_t* pos_off,
+                   const int32_t* pos_val, const int32_t* excl_off, const int32_t* excl_val, const int32_t* cache,
+                   int C, const float* jac, size_t jac_ld, int pos_pool, int32_t* cand, size_t cand_ld,
+                   int32_t* cand_len, int32_t* cache_pos, int32_t* pos_ranked, float* pos_jac, void* ws,
+                   size_t ws_bytes, void* stream);
+
 /* ---- recall counting ---------------------------------------------------------------- *
  * Replaces the per-query Python loop of evaluate_all and spatial_nms
  * (ibl/evaluators.py:132-140, 149-160).  For every query, the rank (0-based, inside the

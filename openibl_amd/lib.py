@@ -166,6 +166,10 @@ SIGNATURES = {
     "oibl_row_argsort_workspace_bytes": (c_size_t, [c_int, c_int]),
     "oibl_row_argsort": (c_int, [c_void_p, c_int, c_int, c_size_t, c_void_p, c_void_p, c_void_p, c_size_t,
                                  c_void_p]),
+    "oibl_mine_rows_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "oibl_mine_rows": (c_int, [c_void_p, c_int, c_int, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                               c_void_p, c_int, c_void_p, c_size_t, c_int, c_void_p, c_size_t, c_void_p, c_void_p,
+                               c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "oibl_cluster_means": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "oibl_local_descriptors": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     "oibl_assign_gap_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),

@@ -1199,6 +1199,90 @@ def row_argsort(vals: torch.Tensor, want_values: bool = False, max_ws_bytes: int
     return (idx, sv) if want_values else idx
 
 
+MINE_MAX_CACHE = 64          # C of oibl_mine_rows
+MINE_MAX_POS_POOL = 1024     # pos_pool of oibl_mine_rows
+MINE_LDS_EXCL = 4096         # exclusion entries per anchor the kernel searches in LDS (longer: global memory)
+
+
+def mine_rows(dist: torch.Tensor, pos_off: torch.Tensor, pos_val: torch.Tensor, excl_off: torch.Tensor,
+              excl_val: torch.Tensor, cache: Optional[torch.Tensor] = None, pos_pool: int = 1,
+              jac: Optional[torch.Tensor] = None, csr_row: Optional[torch.Tensor] = None,
+              max_ws_bytes: int = 1 << 31):
+    """Hard-negative mining of the A anchor rows dist [A][G] (float32, device): oibl_mine_rows.
+
+    pos_* / excl_* are CSR lists (int32, device; every row ascending, without repeats, inside [0, G)) with one row
+    per anchor, or, with csr_row [A] int32, with any number of rows of which csr_row[a] belongs to anchor a.
+    cache [A][C] int32 (-1 = none), jac [A][G] float32 are optional.  Returns (cand [A][G], cand_len [A],
+    cache_pos [A][C], pos_ranked [A][pos_pool], pos_jac [A][pos_pool] or None), int32 but for pos_jac, on the
+    device.  Rows are mined in groups so that the workspace (20 bytes per element) stays below `max_ws_bytes`."""
+    if not dist.is_cuda:
+        raise _lib.OpenIBLAmdError("openibl_amd: mine_rows runs only on an AMD GPU (there is no CPU fallback)")
+    if dist.dtype != torch.float32 or dist.dim() != 2 or (dist.shape[1] > 1 and dist.stride(1) != 1):
+        raise ValueError("mine_rows expects a float32 [A][G] tensor with unit column stride")
+    dev = _need_cuda(pos_off, pos_val, excl_off, excl_val, cache, csr_row)
+    if dev != dist.device:
+        raise ValueError("openibl_amd: tensors on different devices")
+    A, G = map(int, dist.shape)
+    for t in (pos_off, pos_val, excl_off, excl_val, cache, csr_row):
+        if t is not None and t.dtype != torch.int32:
+            raise ValueError("mine_rows expects int32 lists, cache and csr_row")
+    rows = int(pos_off.numel()) - 1
+    if pos_off.dim() != 1 or excl_off.dim() != 1 or int(excl_off.numel()) != rows + 1 or rows < 0:
+        raise ValueError("mine_rows: pos_off and excl_off must have one entry per CSR row plus one")
+    if csr_row is None and rows != A:
+        raise ValueError(f"mine_rows: {rows} CSR rows for {A} anchors (pass csr_row to select rows)")
+    if csr_row is not None and tuple(csr_row.shape) != (A,):
+        raise ValueError("mine_rows: csr_row must have one entry per anchor")
+    C = 0 if cache is None else int(cache.shape[1])
+    if cache is not None and (cache.dim() != 2 or int(cache.shape[0]) != A):
+        raise ValueError("mine_rows: cache must be [A][C]")
+    if C > MINE_MAX_CACHE or not 1 <= int(pos_pool) <= MINE_MAX_POS_POOL:
+        raise ValueError(f"mine_rows: C <= {MINE_MAX_CACHE} and 1 <= pos_pool <= {MINE_MAX_POS_POOL}")
+    if jac is not None and (not jac.is_cuda or jac.device != dev or jac.dtype != torch.float32
+                            or tuple(jac.shape) != (A, G) or (G > 1 and jac.stride(1) != 1)):
+        raise ValueError("mine_rows: jac must be a float32 [A][G] device tensor with unit column stride")
+    pos_pool = int(pos_pool)
+    cand = torch.empty((A, G), dtype=torch.int32, device=dev)
+    cand_len = torch.empty((A,), dtype=torch.int32, device=dev)
+    cache_pos = torch.empty((A, C), dtype=torch.int32, device=dev)
+    pos_ranked = torch.empty((A, pos_pool), dtype=torch.int32, device=dev)
+    pos_jac = torch.empty((A, pos_pool), dtype=torch.float32, device=dev) if jac is not None else None
+    if A == 0 or G == 0:
+        return cand, cand_len, cache_pos, pos_ranked, pos_jac
+    # the kernel trusts the lists (they live on the device): one check of their frame here, one sync
+    ok = torch.ones((), dtype=torch.bool, device=dev)
+    for off, val in ((pos_off, pos_val), (excl_off, excl_val)):
+        ok = ok & (off[0] >= 0) & (off[-1] <= val.numel()) & (off[1:] >= off[:-1]).all()
+        if val.numel():
+            ok = ok & (val.min() >= 0) & (val.max() < G)
+    if csr_row is not None:
+        ok = ok & (csr_row.min() >= 0) & (csr_row.max() < rows)
+    if not bool(ok):
+        raise ValueError("mine_rows: CSR offsets must ascend inside their value arrays, values lie in [0, G), "
+                         "csr_row in [0, rows)")
+    if pos_val.numel() == 0 or excl_val.numel() == 0:     # (an empty tensor has no address to pass)
+        none = torch.zeros((1,), dtype=torch.int32, device=dev)
+        pos_val = pos_val if pos_val.numel() else none
+        excl_val = excl_val if excl_val.numel() else none
+    lib = _lib.load()
+    group = max(1, min(A, int(max_ws_bytes // (20 * G + 2048))))
+    ws = workspace(lib.oibl_mine_rows_workspace_bytes(group, G), dev, "mining")
+    for r0 in range(0, A, group):
+        r = min(group, A - r0)
+        # without csr_row the offsets of row r0 onward are the same arrays advanced by r0 entries
+        _lib.check(lib.oibl_mine_rows(
+            dist[r0:].data_ptr(), r, G, int(dist.stride(0)),
+            None if csr_row is None else csr_row[r0:].data_ptr(),
+            pos_off.data_ptr() + (4 * r0 if csr_row is None else 0), _ptr(pos_val),
+            excl_off.data_ptr() + (4 * r0 if csr_row is None else 0), _ptr(excl_val),
+            None if cache is None or C == 0 else cache[r0:].data_ptr(), C,
+            None if jac is None else jac[r0:].data_ptr(), 0 if jac is None else int(jac.stride(0)), pos_pool,
+            cand[r0:].data_ptr(), G, cand_len[r0:].data_ptr(),
+            None if C == 0 else cache_pos[r0:].data_ptr(), pos_ranked[r0:].data_ptr(),
+            None if pos_jac is None else pos_jac[r0:].data_ptr(), _ptr(ws), ws.numel(), _stream(dev)), "mine_rows")
+    return cand, cand_len, cache_pos, pos_ranked, pos_jac
+
+
 def first_hit_rank(topk_idx: torch.Tensor, gt_offsets: torch.Tensor, gt_values: torch.Tensor,
                    gallery_pids: Optional[torch.Tensor] = None, nms_window: int = 120) -> torch.Tensor:
     """Per query: rank of the first prediction that is a ground-truth neighbour (-1: none), with
