@@ -71,6 +71,35 @@ struct HaloParams {
   float bias_mul = 1.f, out_mul = 1.f;   // the f16mx backbone's activation scale (conv_ring.h, RingParams)
 };
 
+// Row map of the f16mx epilogue (conv_mx_epilogue.h) for both halo kernels: tile row r is a pixel (pooled: a quad)
+// of the patch at (y0, x0) of image img, not a run of the flattened tensor; n0 = the tile's first channel.
+template <bool POOL>
+struct HaloRowMap {
+  char* obase;
+  long orow_bytes, irow;   // irow: output rows (of Wo pixels) in front of the image
+  unsigned pw_mul, pw_sh;
+  int Ho, Wo, oy0, ox0, opw, orows;
+  __device__ __forceinline__ HaloRowMap(const HaloParams& p, int n0, unsigned img, int y0, int x0)
+      : obase(reinterpret_cast<char*>(p.out) + (long)n0 * 4), orow_bytes((long)p.cout * 4), pw_mul(p.pw_mul),
+        pw_sh(p.pw_sh), Ho(POOL ? (p.H >> 1) : p.H), Wo(POOL ? (p.W >> 1) : p.W), oy0(POOL ? (y0 >> 1) : y0),
+        ox0(POOL ? (x0 >> 1) : x0), opw(POOL ? (p.PW >> 1) : p.PW), orows(POOL ? (p.PH * p.PW) >> 2 : p.PH * p.PW) {
+    irow = (long)img * Ho;
+  }
+  __device__ __forceinline__ HaloRowMap at_byte(int b) const {
+    HaloRowMap m = *this;
+    m.obase += b;
+    return m;
+  }
+  __device__ __forceinline__ void store(int r, const uint4& v) const {
+    const int ry = (int)ring_div_u31((unsigned)r, pw_mul, pw_sh), rx = r - ry * opw;
+    const int oy = oy0 + ry, ox = ox0 + rx;
+    if (r < orows && oy < Ho && ox < Wo) {
+      const long orow = (irow + oy) * Wo + ox;
+      *reinterpret_cast<uint4*>(obase + orow * orow_bytes) = v;
+    }
+  }
+};
+
 // one phase's matrix work on two 32x32 accumulator tiles (ring_core.h, compute)
 template <int P, bool SWAP, typename Prep>
 __device__ static inline void halo_phase_mma(f32x16_t& acc0, f32x16_t& acc1, const bf16x8_t (&fa)[2][4],
@@ -293,34 +322,8 @@ __device__ __forceinline__ void conv3x3_halo_body(const HaloParams& p, char* sme
     __builtin_amdgcn_sched_barrier(0);
   };
 
-  // accumulators start at the bias (conv_ring.h)
   f32x16_t acc[4][2];
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    if constexpr (POOL) {
-      float b = p.bias[n0 + wn * 64 + j * 32 + (lane & 31)] * p.bias_mul;
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          asm volatile("" : "+v"(b));
-          acc[i][j][r] = b;
-        }
-    } else {
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        float4 b = *reinterpret_cast<const float4*>(p.bias + n0 + wn * 64 + j * 32 + 8 * g + 4 * (lane >> 5));
-        b = make_float4(b.x * p.bias_mul, b.y * p.bias_mul, b.z * p.bias_mul, b.w * p.bias_mul);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          acc[i][j][4 * g] = b.x;
-          acc[i][j][4 * g + 1] = b.y;
-          acc[i][j][4 * g + 2] = b.z;
-          acc[i][j][4 * g + 3] = b.w;
-        }
-      }
-    }
-  }
+  conv_acc_init_bias<POOL>(acc, p.bias, n0 + wn * 64, p.bias_mul, lane);
 
   using I0 = std::integral_constant<int, 0>;
   using I1 = std::integral_constant<int, 1>;
@@ -414,114 +417,12 @@ __device__ __forceinline__ void conv3x3_halo_body(const HaloParams& p, char* sme
 #undef HALO_IC
   wait_vmcnt<0>();  // (sink writes of the last dummies)
   __syncthreads();
-  if (p.out_mul != 1.f) {   // (uniform; the layer handing the fp32 map to the head: conv_ring.h)
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[i][j][r] *= p.out_mul;
-  }
-
-  // ---- epilogue: as the f16mx ring kernel's (conv_ring.h) — fp32 staging with the chunk swizzle, one
-  //      thread per (row, 32-channel group) packs its f16mx line in place, full lines out — except that
-  //      a tile row is a pixel (pooled: a quad) of the patch, not a run of the flattened tensor.
+  // (the barrier: the halo and weight buffers are free for the epilogue's staging)
+  conv_acc_scale(acc, p.out_mul);
   static_assert(MX, "halo kernel epilogue: f16mx");
-  constexpr int CPR = G::BN / 4;
-  constexpr int ROWB = G::BN * 4;
-  constexpr int PASSES = POOL ? 1 : 2;
-  constexpr int ROWS = (POOL ? G::BM / 4 : G::BM) / PASSES;
-  constexpr int ITEMS = ROWS * (G::BN / 32);
-  constexpr int ITERS = ROWS * CPR / 512, BATCH = 8;
-  static_assert(ITEMS % 512 == 0 && ITERS % BATCH == 0, "epilogue shape");
-  char* obase = reinterpret_cast<char*>(p.out) + (long)n0 * 4;
-  const long orow_bytes = (long)p.cout * 4;
-  const float floor_v = p.relu ? 0.f : -INFINITY;
-  const int Ho = POOL ? (p.H >> 1) : p.H, Wo = POOL ? (p.W >> 1) : p.W;
-  const int oy0 = POOL ? (y0 >> 1) : y0, ox0 = POOL ? (x0 >> 1) : x0;
-  const int opw = POOL ? (p.PW >> 1) : p.PW;
-  const int orows = POOL ? (p.PH * p.PW) >> 2 : p.PH * p.PW;
-#pragma unroll
-  for (int pass = 0; pass < PASSES; ++pass) {
-    if constexpr (POOL) {
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const int col = wn * 64 + j * 32 + (lane & 31);
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-          for (int g = 0; g < 4; ++g) {
-            const float v = fmaxf(fmaxf(fmaxf(acc[i][j][4 * g], acc[i][j][4 * g + 1]),
-                                        fmaxf(acc[i][j][4 * g + 2], acc[i][j][4 * g + 3])), floor_v);
-            const int row = (wm * 4 + i) * 8 + 2 * g + (lane >> 5);
-            *reinterpret_cast<float*>(smem + row * ROWB + (((col >> 2) ^ (row & (CPR - 1))) << 4) + (col & 3) * 4) = v;
-          }
-      }
-    } else {
-      const int half = lane >> 5;
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          const int q = (wn * 64 + j * 32 + 8 * g + 4 * half) >> 2;
-#pragma unroll
-          for (int i2 = 0; i2 < 2; ++i2) {
-            const int i = 2 * pass + i2;
-            const int row = wm * 64 + i2 * 32 + (lane & 31);
-            *reinterpret_cast<float4*>(smem + row * ROWB + ((q ^ (row & (CPR - 1))) << 4)) =
-                make_float4(fmaxf(acc[i][j][4 * g], floor_v), fmaxf(acc[i][j][4 * g + 1], floor_v),
-                            fmaxf(acc[i][j][4 * g + 2], floor_v), fmaxf(acc[i][j][4 * g + 3], floor_v));
-          }
-        }
-    }
-    __syncthreads();
-    if (!p.out_f32) {
-#pragma unroll 1
-      for (int it = 0; it < ITEMS / 512; ++it) {
-        const int item = it * 512 + (int)threadIdx.x;
-        const int row = item % ROWS, grp = item / ROWS;
-        char* const rowp = smem + row * ROWB;
-        const int sw = row & (CPR - 1);
-        float v[32];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-          const float4 t = *reinterpret_cast<const float4*>(rowp + (((grp * 8 + k) ^ sw) << 4));
-          v[4 * k] = t.x;
-          v[4 * k + 1] = t.y;
-          v[4 * k + 2] = t.z;
-          v[4 * k + 3] = t.w;
-        }
-        uint4 line[8];
-        mx_pack_line(v, line, p.range_flag);
-#pragma unroll
-        for (int k = 0; k < 8; ++k) *reinterpret_cast<uint4*>(rowp + (((grp * 8 + k) ^ sw) << 4)) = line[k];
-      }
-      __syncthreads();
-    }
-#pragma unroll
-    for (int it0 = 0; it0 < ITERS; it0 += BATCH) {
-      uint4 v[BATCH];
-#pragma unroll
-      for (int u = 0; u < BATCH; ++u) {
-        const int idx = (it0 + u) * 512 + (int)threadIdx.x;
-        const int lr = idx / CPR, q = idx % CPR;
-        v[u] = *reinterpret_cast<const uint4*>(smem + lr * ROWB + ((q ^ (lr & (CPR - 1))) << 4));
-      }
-#pragma unroll
-      for (int u = 0; u < BATCH; ++u) {
-        const int idx = (it0 + u) * 512 + (int)threadIdx.x;
-        const int lr = idx / CPR;
-        const int r = PASSES == 1 ? lr : (lr >> 6) * 128 + pass * 64 + (lr & 63);  // tile row = pixel / quad
-        const int ry = (int)ring_div_u31((unsigned)r, p.pw_mul, p.pw_sh), rx = r - ry * opw;
-        const int oy = oy0 + ry, ox = ox0 + rx;
-        if (r < orows && oy < Ho && ox < Wo) {
-          const long orow = ((long)img * Ho + oy) * Wo + ox;
-          *reinterpret_cast<uint4*>(obase + orow * orow_bytes + (idx % CPR) * 16) = v[u];
-        }
-      }
-    }
-    if (pass + 1 < PASSES) __syncthreads();
-  }
+  static_assert(conv_mx_epilogue_lds<G::BM, G::BN, POOL>() <= HALO_LDS, "epilogue staging");
+  conv_mx_epilogue<G::BM, G::BN, 512, POOL>(acc, smem, wm, wn, lane, p.relu, p.out_f32, p.range_flag,
+                                            HaloRowMap<POOL>(p, n0, img, y0, x0), [](int, int) {});
 }
 
 template <bool POOL, int P>

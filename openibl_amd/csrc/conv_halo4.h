@@ -228,34 +228,8 @@ __global__ __launch_bounds__(H4_THREADS, 2) void conv3x3_halo4_kernel(HaloParams
     __builtin_amdgcn_sched_barrier(0);
   };
 
-  // accumulators start at the bias (conv_halo.h)
   f32x16_t acc[4][2];
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    if constexpr (POOL) {
-      float b = p.bias[n0 + wn * 64 + j * 32 + (lane & 31)] * p.bias_mul;
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          asm volatile("" : "+v"(b));
-          acc[i][j][r] = b;
-        }
-    } else {
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        float4 b = *reinterpret_cast<const float4*>(p.bias + n0 + wn * 64 + j * 32 + 8 * g + 4 * (lane >> 5));
-        b = make_float4(b.x * p.bias_mul, b.y * p.bias_mul, b.z * p.bias_mul, b.w * p.bias_mul);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          acc[i][j][4 * g] = b.x;
-          acc[i][j][4 * g + 1] = b.y;
-          acc[i][j][4 * g + 2] = b.z;
-          acc[i][j][4 * g + 3] = b.w;
-        }
-      }
-    }
-  }
+  conv_acc_init_bias<POOL>(acc, p.bias, n0 + wn * 64, p.bias_mul, lane);
 
   using I0 = std::integral_constant<int, 0>;
   using I1 = std::integral_constant<int, 1>;
@@ -332,113 +306,12 @@ __global__ __launch_bounds__(H4_THREADS, 2) void conv3x3_halo4_kernel(HaloParams
   wait_vmcnt<0>();  // (sink writes of the last dummies)
   __syncthreads();
   if (wgprof) p.prof[64 + 4 * (size_t)blockIdx.x + 3] = __builtin_amdgcn_s_memtime();
-  if (p.out_mul != 1.f) {   // (uniform; the layer handing the fp32 map to the head — only when the "every layer on
-                            //  this kernel" experiment, hook 13, sends conv5_3 here: conv_halo.h)
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[i][j][r] *= p.out_mul;
-  }
-
-  // ---- epilogue: conv_halo.h's — fp32 staging with the chunk swizzle, one thread per (row, 32-channel group) packs
-  //      its f16mx line in place, full lines out — for 128 channels and 256 threads
-  constexpr int CPR = H4_BN / 4;
-  constexpr int ROWB = H4_BN * 4;
-  constexpr int PASSES = POOL ? 1 : 2;
-  constexpr int ROWS = (POOL ? H4_BM / 4 : H4_BM) / PASSES;
-  constexpr int ITEMS = ROWS * (H4_BN / 32);
-  constexpr int ITERS = ROWS * CPR / H4_THREADS, BATCH = 8;
-  static_assert(ITEMS % H4_THREADS == 0 && ITERS % BATCH == 0 && ROWS * ROWB <= H4_LDS, "epilogue shape");
-  char* obase = reinterpret_cast<char*>(p.out) + (long)n0 * 4;
-  const long orow_bytes = (long)p.cout * 4;
-  const float floor_v = p.relu ? 0.f : -INFINITY;
-  const int Ho = POOL ? (p.H >> 1) : p.H, Wo = POOL ? (p.W >> 1) : p.W;
-  const int oy0 = POOL ? (y0 >> 1) : y0, ox0 = POOL ? (x0 >> 1) : x0;
-  const int opw = POOL ? (p.PW >> 1) : p.PW;
-  const int orows = POOL ? (p.PH * p.PW) >> 2 : p.PH * p.PW;
-#pragma unroll
-  for (int pass = 0; pass < PASSES; ++pass) {
-    if constexpr (POOL) {
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const int col = wn * 64 + j * 32 + (lane & 31);
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-          for (int g = 0; g < 4; ++g) {
-            const float v = fmaxf(fmaxf(fmaxf(acc[i][j][4 * g], acc[i][j][4 * g + 1]),
-                                        fmaxf(acc[i][j][4 * g + 2], acc[i][j][4 * g + 3])), floor_v);
-            const int row = (wm * 4 + i) * 8 + 2 * g + (lane >> 5);
-            *reinterpret_cast<float*>(smem + row * ROWB + (((col >> 2) ^ (row & (CPR - 1))) << 4) + (col & 3) * 4) = v;
-          }
-      }
-    } else {
-      const int half = lane >> 5;
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          const int q = (wn * 64 + j * 32 + 8 * g + 4 * half) >> 2;
-#pragma unroll
-          for (int i2 = 0; i2 < 2; ++i2) {
-            const int i = 2 * pass + i2;
-            const int row = wm * 64 + i2 * 32 + (lane & 31);
-            *reinterpret_cast<float4*>(smem + row * ROWB + ((q ^ (row & (CPR - 1))) << 4)) =
-                make_float4(fmaxf(acc[i][j][4 * g], floor_v), fmaxf(acc[i][j][4 * g + 1], floor_v),
-                            fmaxf(acc[i][j][4 * g + 2], floor_v), fmaxf(acc[i][j][4 * g + 3], floor_v));
-          }
-        }
-    }
-    __syncthreads();
-    if (!p.out_f32) {
-#pragma unroll 1
-      for (int it = 0; it < ITEMS / H4_THREADS; ++it) {
-        const int item = it * H4_THREADS + (int)threadIdx.x;
-        const int row = item % ROWS, grp = item / ROWS;
-        char* const rowp = smem + row * ROWB;
-        const int sw = row & (CPR - 1);
-        float v[32];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-          const float4 t = *reinterpret_cast<const float4*>(rowp + (((grp * 8 + k) ^ sw) << 4));
-          v[4 * k] = t.x;
-          v[4 * k + 1] = t.y;
-          v[4 * k + 2] = t.z;
-          v[4 * k + 3] = t.w;
-        }
-        uint4 line[8];
-        mx_pack_line(v, line, p.range_flag);
-#pragma unroll
-        for (int k = 0; k < 8; ++k) *reinterpret_cast<uint4*>(rowp + (((grp * 8 + k) ^ sw) << 4)) = line[k];
-      }
-      __syncthreads();
-    }
-#pragma unroll
-    for (int it0 = 0; it0 < ITERS; it0 += BATCH) {
-      uint4 v[BATCH];
-#pragma unroll
-      for (int u = 0; u < BATCH; ++u) {
-        const int idx = (it0 + u) * H4_THREADS + (int)threadIdx.x;
-        const int lr = idx / CPR, q = idx % CPR;
-        v[u] = *reinterpret_cast<const uint4*>(smem + lr * ROWB + ((q ^ (lr & (CPR - 1))) << 4));
-      }
-#pragma unroll
-      for (int u = 0; u < BATCH; ++u) {
-        const int idx = (it0 + u) * H4_THREADS + (int)threadIdx.x;
-        const int lr = idx / CPR;
-        const int r = PASSES == 1 ? lr : (lr >> 6) * 128 + pass * 64 + (lr & 63);  // tile row = pixel / quad
-        const int ry = (int)ring_div_u31((unsigned)r, p.pw_mul, p.pw_sh), rx = r - ry * opw;
-        const int oy = oy0 + ry, ox = ox0 + rx;
-        if (r < orows && oy < Ho && ox < Wo) {
-          const long orow = ((long)img * Ho + oy) * Wo + ox;
-          *reinterpret_cast<uint4*>(obase + orow * orow_bytes + (idx % CPR) * 16) = v[u];
-        }
-      }
-    }
-    if (pass + 1 < PASSES) __syncthreads();
-  }
+  // (out_mul != 1 only from a direct caller: the backbone's layer that sets it, conv5_3, has 512 output channels
+  //  and never runs on this kernel)
+  conv_acc_scale(acc, p.out_mul);
+  static_assert(conv_mx_epilogue_lds<H4_BM, H4_BN, POOL>() <= H4_LDS, "epilogue staging");
+  conv_mx_epilogue<H4_BM, H4_BN, H4_THREADS, POOL>(acc, smem, wm, wn, lane, p.relu, p.out_f32, p.range_flag,
+                                                   HaloRowMap<POOL>(p, n0, img, y0, x0), [](int, int) {});
   if (wgprof) p.prof[64 + 4 * (size_t)blockIdx.x + 2] = __builtin_amdgcn_s_memtime();
 }
 

@@ -20,7 +20,7 @@
 // every (pixel, 32-channel group) into its f16mx line (mx_pack_line) before the copy-out.
 #pragma once
 
-#include "ring_core.h"
+#include "conv_mx_epilogue.h"
 
 namespace oibl {
 
@@ -76,6 +76,20 @@ static inline void ring_magic_u31(unsigned d, unsigned* mul, unsigned* sh) {
 __device__ static inline unsigned ring_div_u31(unsigned m, unsigned mul, unsigned sh) {
   return (unsigned)(((unsigned long long)m * mul) >> sh);
 }
+
+// Row map of the f16mx epilogue (conv_mx_epilogue.h): tile row r is row row0 + r of the flattened output tensor;
+// obase = the tile's first channel in row 0 (split-K: of this part's partial tensor).
+struct RingRowMap {
+  long row0;
+  int out_rows;
+  char* obase;
+  long orow_bytes;
+  __device__ __forceinline__ RingRowMap at_byte(int b) const { return {row0, out_rows, obase + b, orow_bytes}; }
+  __device__ __forceinline__ void store(int r, const uint4& v) const {
+    const long grow = row0 + r;
+    if (grow < out_rows) *reinterpret_cast<uint4*>(obase + grow * orow_bytes) = v;
+  }
+};
 
 // epilogue staging: the output tile (X3 without pooling: one half of its rows at a time)
 template <int WM, bool POOL, int P = RING_BF16, bool OUTMX = (P >= RING_MX)>
@@ -332,109 +346,19 @@ __device__ __forceinline__ void conv3x3_ring_body(const RingParams& p, char* sme
   //             fp32 value when out_f32 is set; without pooling the tile is staged in two passes of
   //             BM / 2 rows (accumulator row tiles {0, 1}, then {2, 3} of every wave).
   if constexpr (OUTMX) {
-    // ---- f16mx epilogue.  The tile (without pooling: one half of its rows at a time) is staged as
-    // fp32, rows of BN floats = CPR 16-byte chunks, chunk q of row r at physical chunk q ^ (r % CPR):
-    // the 8 chunks of a (row, 32-channel group) item stay inside one aligned 128-byte block, 16
-    // consecutive rows of one logical chunk fall on 16 distinct bank slots (the accumulator writes
-    // and the item reads walk rows), and a row's chunks read in order are a permutation of the row
-    // (the copy-out walks chunks).  Then one thread per item reads its 32 values, packs the f16mx
-    // line (mx_pack_line) and writes it back in place; the copy-out moves full lines.
-    // out_f32 (the layer feeding the fp32 head): no packing, the fp32 rows go out as they are.
-    constexpr int CPR = G::BN / 4;
-    constexpr int ROWB = G::BN * 4;
-    constexpr int PASSES = POOL ? 1 : 2;
-    constexpr int ROWS = (POOL ? G::BM / 4 : G::BM) / PASSES;
-    constexpr int ITEMS = ROWS * (G::BN / 32);
-    constexpr int ITERS = ROWS * CPR / 512, BATCH = 8;
-    static_assert(ITEMS % 512 == 0 && ITERS % BATCH == 0, "f16mx epilogue shape");
+    // ---- f16mx epilogue (conv_mx_epilogue.h)
     // (split-K: the partial tensor of this K range, rows counted from m_base)
-    const long row0 = (POOL ? (m0 >> 2) : m0) - (splitk ? p.m_base : 0);
-    char* obase = reinterpret_cast<char*>(p.out) + (long)n0 * 4 + (splitk ? (size_t)blockIdx.y * p.part_stride : 0);
-    const long orow_bytes = (long)p.cout * 4;
-    const float floor_v = p.relu ? 0.f : -INFINITY;
+    const RingRowMap rows = {
+        (POOL ? (m0 >> 2) : m0) - (splitk ? p.m_base : 0), p.out_rows,
+        reinterpret_cast<char*>(p.out) + (long)n0 * 4 + (splitk ? (size_t)blockIdx.y * p.part_stride : 0),
+        (long)p.cout * 4};
     unsigned long long t_copy = 0;
-    unsigned long long ep_[6] = {};
-#pragma unroll
-    for (int pass = 0; pass < PASSES; ++pass) {
-      if constexpr (POOL) {
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          const int col = wn * 64 + j * 32 + (lane & 31);
-#pragma unroll
-          for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-              const float v = fmaxf(fmaxf(fmaxf(acc[i][j][4 * g], acc[i][j][4 * g + 1]),
-                                          fmaxf(acc[i][j][4 * g + 2], acc[i][j][4 * g + 3])), floor_v);
-              const int row = (wm * 4 + i) * 8 + 2 * g + (lane >> 5);
-              *reinterpret_cast<float*>(smem + row * ROWB + (((col >> 2) ^ (row & (CPR - 1))) << 4) + (col & 3) * 4) = v;
-            }
-        }
-      } else {
-        const int half = lane >> 5;
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-          for (int g = 0; g < 4; ++g) {
-            const int q = (wn * 64 + j * 32 + 8 * g + 4 * half) >> 2;  // chunk of this quad's 4 channels
-#pragma unroll
-            for (int i2 = 0; i2 < 2; ++i2) {
-              const int i = 2 * pass + i2;
-              const int row = wm * 64 + i2 * 32 + (lane & 31);
-              *reinterpret_cast<float4*>(smem + row * ROWB + ((q ^ (row & (CPR - 1))) << 4)) =
-                  make_float4(fmaxf(acc[i][j][4 * g], floor_v), fmaxf(acc[i][j][4 * g + 1], floor_v),
-                              fmaxf(acc[i][j][4 * g + 2], floor_v), fmaxf(acc[i][j][4 * g + 3], floor_v));
-            }
-          }
-      }
-      __syncthreads();
-      if (pass == 0 && prof) t_copy = __builtin_amdgcn_s_memtime();
-      if (prof) ep_[3 * pass] = __builtin_amdgcn_s_memtime();       // staged
-      if (!p.out_f32) {
-#pragma unroll 1
-        for (int it = 0; it < ITEMS / 512; ++it) {
-          const int item = it * 512 + (int)threadIdx.x;
-          const int row = item % ROWS, grp = item / ROWS;
-          char* const rowp = smem + row * ROWB;
-          const int sw = row & (CPR - 1);
-          float v[32];
-#pragma unroll
-          for (int k = 0; k < 8; ++k) {
-            const float4 t = *reinterpret_cast<const float4*>(rowp + (((grp * 8 + k) ^ sw) << 4));
-            v[4 * k] = t.x;
-            v[4 * k + 1] = t.y;
-            v[4 * k + 2] = t.z;
-            v[4 * k + 3] = t.w;
-          }
-          uint4 line[8];
-          mx_pack_line(v, line, p.range_flag);
-#pragma unroll
-          for (int k = 0; k < 8; ++k) *reinterpret_cast<uint4*>(rowp + (((grp * 8 + k) ^ sw) << 4)) = line[k];
-        }
-        __syncthreads();
-      }
-      if (prof) ep_[3 * pass + 1] = __builtin_amdgcn_s_memtime();   // packed
-#pragma unroll
-      for (int it0 = 0; it0 < ITERS; it0 += BATCH) {
-        uint4 v[BATCH];
-#pragma unroll
-        for (int u = 0; u < BATCH; ++u) {
-          const int idx = (it0 + u) * 512 + (int)threadIdx.x;
-          const int lr = idx / CPR, q = idx % CPR;
-          v[u] = *reinterpret_cast<const uint4*>(smem + lr * ROWB + ((q ^ (lr & (CPR - 1))) << 4));
-        }
-#pragma unroll
-        for (int u = 0; u < BATCH; ++u) {
-          const int idx = (it0 + u) * 512 + (int)threadIdx.x;
-          const int lr = idx / CPR;
-          const long grow = row0 + (PASSES == 1 ? lr : (lr >> 6) * 128 + pass * 64 + (lr & 63));
-          if (grow < p.out_rows)
-            *reinterpret_cast<uint4*>(obase + grow * orow_bytes + (idx % CPR) * 16) = v[u];
-        }
-      }
-      if (prof) ep_[3 * pass + 2] = __builtin_amdgcn_s_memtime();   // stores issued
-      if (pass + 1 < PASSES) __syncthreads();
-    }
+    unsigned long long ep_[6] = {};   // per pass: staged, packed, stores issued
+    auto stamp = [&](int pass, int k) __attribute__((always_inline)) {
+      if (pass == 0 && k == 0 && prof) t_copy = __builtin_amdgcn_s_memtime();
+      if (prof) ep_[3 * pass + k] = __builtin_amdgcn_s_memtime();
+    };
+    conv_mx_epilogue<G::BM, G::BN, 512, POOL>(acc, smem, wm, wn, lane, p.relu, p.out_f32, p.range_flag, rows, stamp);
     if (prof) {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       const unsigned long long t_end = __builtin_amdgcn_s_memtime();
@@ -445,8 +369,8 @@ __device__ __forceinline__ void conv3x3_ring_body(const RingParams& p, char* sme
         p.prof[3] = t_end - t_copy;
         p.prof[4] = ep_[1] - ep_[0];   // pass 0: pack
         p.prof[5] = ep_[2] - ep_[1];   //         copy-out (issue)
-        p.prof[6] = PASSES > 1 ? ep_[4] - ep_[3] : 0;
-        p.prof[7] = PASSES > 1 ? ep_[5] - ep_[4] : 0;
+        p.prof[6] = POOL ? 0 : ep_[4] - ep_[3];   // pass 1 (no pooling)
+        p.prof[7] = POOL ? 0 : ep_[5] - ep_[4];
       }
     }
     if (wgprof) p.prof[64 + 4 * (size_t)blockIdx.x + 2] = __builtin_amdgcn_s_memtime();   // (stores issued, not drained)

@@ -200,6 +200,46 @@ def test_mx_batch_rows_independent_and_graphed(model, dev):
     assert torch.equal(a, want) and torch.equal(b, want)
 
 
+@pytest.fixture(scope="module")
+def head_map_case(state_dict):
+    """2 x 128 x 160 images: the conv5 map is 8 x 10 — 160 rows of one 256-row ring tile, one 80-pixel patch per
+    image for the halo kernel: both staging passes of the epilogue run, with masked rows."""
+    x = synth.images(2, 128, 160, seed=128160)
+    with torch.no_grad():
+        return x, od.embednetpca(x, state_dict)
+
+
+@pytest.mark.parametrize("variant,splitk", [(0, 1), (1, 0), (1, 1), (3, 1)],
+                         ids=["default", "ring-one-pass", "ring-split", "halo"])
+def test_fp32_head_map_through_every_conv5_3_route(model, dev, head_map_case, variant, splitk):
+    """conv5_3 hands the head an fp32 map (out_f32 = 1) and undoes the activation scale (out_mul = 8); the
+    single-layer tests never set either (ops.conv3x3_nhwc).  Its routes through launch_conv_mx at this size:
+    default       -> launch_conv_mx_split: two 256 x 256 tiles x 9 K parts through the ring epilogue (fp32 rows at
+                     the part offset, out_mul 1), scaled by conv_mx_splitk_reduce8_kernel;
+    ring-one-pass -> mx_variant 1, mx_splitk 0: launch_conv_ring<2, false, RING_MX>, out_f32 and out_mul in the
+                     ring kernel's own epilogue;
+    ring-split    -> mx_variant 1, mx_splitk 1: conv5_3 as in default, conv2_x / conv3_x on the ring kernels
+                     instead of the halo kernels;
+    halo          -> mx_variant 3: no split; launch_conv_halo<false>, out_f32 and out_mul in the halo kernel.
+    Each within 1e-4 of the oracle, without a range fallback, and the same bits when run again."""
+    from openibl_amd import lib
+    x, want = head_map_case
+    xd, vgg, h = x.to(dev), model.base_model, lib.debug_hooks()
+    fallbacks = vgg.range_fallbacks
+    h.oibl_debug_set_mx_variant(variant)
+    h.oibl_debug_set_mx_splitk(splitk)
+    try:
+        assert vgg.effective_precision(xd) == "f16mx"
+        got = model(xd).clone()
+        again = model(xd).clone()
+    finally:
+        h.oibl_debug_set_mx_variant(0)
+        h.oibl_debug_set_mx_splitk(1)
+    assert vgg.range_fallbacks == fallbacks
+    _assert_desc(f"desc f16mx, conv5_3 route (mx_variant {variant}, mx_splitk {splitk})", got.cpu(), want)
+    assert torch.equal(again, got)
+
+
 @pytest.mark.parametrize("N,H,W", [(1, 8, 32), (2, 16, 64), (1, 21, 45), (3, 30, 70), (1, 2, 3), (2, 3, 4),
                                    (2, 9, 33), (1, 64, 96), (5, 40, 136), (1, 17, 65)])
 def test_vgg_stem_mx_fused(dev, N, H, W):
