@@ -2,7 +2,7 @@
 // Reference behaviour: pairwise_distance (ibl/evaluators.py:105-130) and the argsort consumed by
 // evaluate_all (ibl/evaluators.py:142-159).
 #include "gemm_core.h"
-#include "ring_core.h"
+#include "match_ring.h"
 
 namespace oibl {
 
@@ -184,211 +184,7 @@ __global__ __launch_bounds__(Cfg::NTHREADS) void pairwise_kernel(PairParams p) {
   }
 }
 
-// ---------------------------------------------------------------------------------------------
-// bf16 distance kernel on the ring schedule (ring_core.h): 256 x 256 tile, A = queries, B = gallery,
-// K = d.  Same K order and the same epilogue expression as pairwise_kernel -> identical matrices.
-// Tile order: the hardware deals block b to XCD b % 8; every XCD gets a contiguous range of tile
-// ids, and ids walk groups of 8 query tiles x all gallery tiles with the query tile fastest, so the
-// 32 workgroups resident on an XCD form an 8 x 4 block of tiles that shares 8 query panels and 4
-// gallery panels through that XCD's L2 (12 panel streams for 32 tiles instead of 33-64).
-//   FILTER = false: write dist[m][ldd].
-//   FILTER = true : fused top-k front end.  thr[row] is an upper bound of the row's k-th smallest
-//     distance (k-th smallest over a strided sample of the gallery, computed with this same kernel,
-//     so the sample's own distances reappear bit for bit); every distance <= thr[row] is appended
-//     to the row's candidate list (value, global index).  The matrix is never written: for
-//     8192 x 81920 the candidates are ~1 % of its 2.7 GB.  Lists that outgrow `cap` are counted,
-//     not stored (the caller sees cnt > cap and falls back to the exact path).
-// ---------------------------------------------------------------------------------------------
-struct PairRingParams {
-  const void* x;  // [m][d] bf16
-  const void* y;  // [n rows at y_row_bytes][d] bf16
-  const float* xn;
-  const float* yn;  // yn[col * yn_stride]
-  float* dist;
-  size_t ldd;
-  unsigned x_bytes, y_bytes;
-  long y_row_bytes;
-  int yn_stride;
-  int m, n, d, tiles_m, tiles_n;
-  const float* thr;  // thr[row * thr_stride]
-  int thr_stride;
-  float* cand_val;
-  int32_t* cand_idx;
-  int* cand_cnt;
-  int cap, index_base, index_stride;  // global index of column c = index_base + c * index_stride
-  int group_m;                        // query tiles per ordering group (see above)
-  // 2-way split-K (threshold sample only, gridDim.y = 2): block (., h) contracts K-half h and writes
-  // dist + h * part_stride; the norms enter half 0 only, so the two halves ADD UP to the distances
-  // (in another summation order than the one-pass kernel: see thr_slack).
-  size_t part_stride;
-  // !FILTER: optional, max over the launch's columns of yn (bit pattern of a non-negative float,
-  // atomicMax).  FILTER: optional, read back — the threshold of row i is widened by
-  // thr_slack * (xn[i] + *yn_max) / 2, a bound on what the other summation order can move a distance.
-  unsigned* yn_max;
-  float thr_slack;
-};
-
-template <bool FILTER, int P = RING_BF16>
-__global__ __launch_bounds__(512) void pairwise_ring_kernel(PairRingParams p) {
-  using G = RingGeo<2>;
-  constexpr bool X3 = P != RING_BF16;  // 4-byte operand elements, 32 K per K-tile (bf16x3 and f16mx)
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int wm = wave / G::WN, wn = wave % G::WN;
-  const unsigned id = xcd_remap(blockIdx.x, gridDim.x);
-  const unsigned gm = (unsigned)p.group_m;
-  const unsigned width = gm * (unsigned)p.tiles_n;
-  const unsigned grp = id / width, in_grp = id - grp * width;
-  const unsigned first_m = grp * gm;
-  const unsigned gsz = (unsigned)p.tiles_m - first_m < gm ? (unsigned)p.tiles_m - first_m : gm;
-  const int tm = (int)(first_m + in_grp % gsz), tn = (int)(in_grp / gsz);
-  const int m0 = tm * G::BM, n0 = tn * G::BN;
-
-  const int piece = ring_piece(wave, lane);
-  int rows_a[4], rows_b[4];
-#pragma unroll
-  for (int h = 0; h < 2; ++h)
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      rows_a[2 * h + i] = ring_a_row<2>(wave, lane, h, i);
-      rows_b[2 * h + i] = ring_b_row<2>(wave, lane, h, i);
-    }
-  // split-K: this block's K-half starts kh * d/2 elements into every row
-  const int ksplit = (int)gridDim.y, kh = (int)blockIdx.y;
-  const int d_part = p.d / ksplit;
-  const unsigned koff = (unsigned)kh * (unsigned)d_part * (X3 ? 4u : 2u);
-  RingRowLoader<2> la, lb;
-  la.init(static_cast<const char*>(p.x) + koff, p.x_bytes - koff, m0, p.m, (long)p.d * (X3 ? 4 : 2), rows_a,
-          piece);
-  lb.init(static_cast<const char*>(p.y) + koff, p.y_bytes - koff, n0, p.n, p.y_row_bytes, rows_b,
-          P >= RING_MX ? ring_piece_mxb(wave, lane) : piece);
-
-  f32x16_t acc[4][2];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-  // one copy of the loop per stagger group (ring_core.h)
-  if ((wave >> 2) == 0) ring_mainloop<2, false, false, P, 0>(acc, smem, wave, lane, la, lb, d_part >> (X3 ? 5 : 6));
-  else ring_mainloop<2, false, false, P, 1>(acc, smem, wave, lane, la, lb, d_part >> (X3 ? 5 : 6));
-
-  // norms (and thresholds) of the tile's rows / columns -> LDS; out-of-range rows/columns are
-  // clamped here and masked at the store
-  float* const xn_s = reinterpret_cast<float*>(smem);
-  float* const yn_s = xn_s + 256;
-  float* const th_s = xn_s + 512;
-  if (threadIdx.x < 256) {
-    int r = m0 + (int)threadIdx.x;
-    if (r > p.m - 1) r = p.m - 1;
-    const float xn = p.xn[r];
-    xn_s[threadIdx.x] = kh == 0 ? xn : 0.f;
-    if (FILTER) {
-      float th = p.thr[(long)r * p.thr_stride];
-      if (p.yn_max) th += p.thr_slack * 0.5f * (xn + __uint_as_float(*p.yn_max));
-      th_s[threadIdx.x] = th;
-    }
-  } else {
-    int c = n0 + (int)threadIdx.x - 256;
-    if (c > p.n - 1) c = p.n - 1;
-    const float yn = p.yn[(long)c * p.yn_stride];
-    yn_s[threadIdx.x - 256] = kh == 0 ? yn : 0.f;
-    if (!FILTER && p.yn_max && kh == 0 && tm == 0) {  // one column of tiles covers every column once
-      const float mx = wave_max(yn);                  // (norms are >= 0: their bit patterns order as integers)
-      if (lane == 0) atomicMax(p.yn_max, __float_as_uint(mx));
-    }
-  }
-  __syncthreads();
-  // lane geometry: column col0 + 32 j, rows row0 + 32 i + (r & 3) + 8 (r >> 2)
-  const int col0 = wn * 64 + (lane & 31), row0 = wm * 128 + 4 * (lane >> 5);
-  if constexpr (!FILTER) {
-    // stores go through buffer descriptors based at the first element of each 32-row accumulator tile of
-    // the wave: one 32-bit lane offset, everything else is scalar (offsets inside a tile stay below
-    // 31 * ldd * 4 bytes: the host guarantees ldd <= 2^24)
-    const float* const dbase = p.dist + (size_t)kh * p.part_stride + ((size_t)m0 + wm * 128) * p.ldd + n0;
-    const unsigned ldd4 = (unsigned)p.ldd * 4u;
-    const unsigned voff = (unsigned)(4 * (lane >> 5)) * ldd4 + (unsigned)col0 * 4u;
-    const int rows_left = p.m - m0 - row0;  // row r of this lane is valid iff its offset < rows_left
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const __amdgpu_buffer_rsrc_t rs_d = __builtin_amdgcn_make_buffer_rsrc(
-          const_cast<float*>(dbase + (size_t)(32 * i) * p.ldd), 0, 0x7fffffff, 0x00020000);
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const bool nok = n0 + col0 + 32 * j < p.n;
-        const float yn = yn_s[col0 + 32 * j];
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int rt = (r & 3) + 8 * (r >> 2), ro = 32 * i + rt;
-          const float dv = fmaf(-2.0f, acc[i][j][r], xn_s[row0 + ro] + yn);
-          if (nok && ro < rows_left)
-            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, dv), rs_d, (int)voff,
-                                                  (int)((unsigned)rt * ldd4 + 128u * j), 0);
-          // keep the scalar row offsets from being computed (and spilled) for all 128 stores at once
-          if ((r & 7) == 7) __builtin_amdgcn_sched_barrier(0);
-        }
-      }
-    }
-  } else {
-    // Survivors are rare (about 1 % of the distances, ~1.3 per lane and tile) but a wave sees one
-    // in every second accumulator register, so nothing with a memory round trip may sit in this
-    // loop: each lane first collects its own survivors in a private LDS list (count in a
-    // register), then all lanes claim their slots with back-to-back atomics — one round trip per
-    // tile instead of one per register.  List layout [entry][thread]: conflict-free.
-    constexpr int LCAP = 8;
-    float* const l_val = reinterpret_cast<float*>(smem + 4096);
-    int* const l_idx = reinterpret_cast<int*>(smem + 4096 + LCAP * 512 * 4);
-    int* const l_row = reinterpret_cast<int*>(smem + 4096 + 2 * LCAP * 512 * 4);
-    const int rows_left = p.m - m0 - row0;
-    int nl = 0;
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int n = n0 + col0 + 32 * j;
-      const bool nok = n < p.n;
-      const float yn = yn_s[col0 + 32 * j];
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int ro = 32 * i + (r & 3) + 8 * (r >> 2);
-          const float dv = fmaf(-2.0f, acc[i][j][r], xn_s[row0 + ro] + yn);
-          if (nok && ro < rows_left && dv <= th_s[row0 + ro]) {
-            const int m = m0 + row0 + ro;
-            if (nl < LCAP) {
-              l_val[nl * 512 + threadIdx.x] = dv;
-              l_idx[nl * 512 + threadIdx.x] = p.index_base + n * p.index_stride;
-              l_row[nl * 512 + threadIdx.x] = m;
-              ++nl;
-            } else {  // list full (practically never): claim the slot right away
-              const int pos = atomicAdd(p.cand_cnt + m, 1);
-              if (pos < p.cap) {
-                p.cand_val[(size_t)m * p.cap + pos] = dv;
-                p.cand_idx[(size_t)m * p.cap + pos] = p.index_base + n * p.index_stride;
-              }
-            }
-          }
-        }
-    }
-    int e_row[LCAP], e_pos[LCAP];
-#pragma unroll
-    for (int e = 0; e < LCAP; ++e) {
-      e_row[e] = e < nl ? l_row[e * 512 + threadIdx.x] : 0;
-      e_pos[e] = p.cap;
-    }
-#pragma unroll
-    for (int e = 0; e < LCAP; ++e)
-      if (e < nl) e_pos[e] = atomicAdd(p.cand_cnt + e_row[e], 1);
-#pragma unroll
-    for (int e = 0; e < LCAP; ++e)
-      if (e < nl && e_pos[e] < p.cap) {
-        p.cand_val[(size_t)e_row[e] * p.cap + e_pos[e]] = l_val[e * 512 + threadIdx.x];
-        p.cand_idx[(size_t)e_row[e] * p.cap + e_pos[e]] = l_idx[e * 512 + threadIdx.x];
-      }
-  }
-}
+// (the distance kernels on the ring schedule, pairwise_ring_kernel<FILTER, P> and its parameters: match_ring.h)
 
 // ---------------------------------------------------------------------------------------------
 // per-row top-k (k smallest, ascending, lowest index first on ties)
@@ -958,20 +754,31 @@ static bool pair_ring_wanted(int m, int n, int d, int es = 2) {
   return g_match_ring == 2 || (long)((m + 255) / 256) * ((n + 255) / 256) >= 64;
 }
 
+// One launch of a ring distance kernel (match_ring.h, match_f16r.h): tile counts and order, grid check, LDS limit.
+// The kernel is a template argument: OIBL_SET_MAX_LDS remembers per kernel what it has done.
 extern "C++" {
-template <bool FILTER, int P = RING_BF16>
-static int launch_pairwise_ring(PairRingParams& p, hipStream_t st, int ksplit = 1) {
+template <typename Params>
+using RingDistLaunch = int (*)(Params& p, hipStream_t st, int ksplit, const char* who);
+
+template <auto KERN, typename Params>
+static int launch_ring_dist(Params& p, hipStream_t st, int ksplit, const char* who) {
   p.tiles_m = (p.m + 255) / 256;
   p.tiles_n = (p.n + 255) / 256;
   p.group_m = g_match_group;
   const long grid = (long)p.tiles_m * p.tiles_n;
-  OIBL_REQUIRE(grid > 0 && grid <= 0x7fffffffL, "pairwise: grid out of range");
+  OIBL_REQUIRE(grid > 0 && grid <= 0x7fffffffL, "%s: grid out of range", who);
   constexpr int lds = RingGeo<2>::MAIN_LDS;
-  auto kern = pairwise_ring_kernel<FILTER, P>;
-  OIBL_SET_MAX_LDS(kern, lds);
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid, (unsigned)ksplit), dim3(512), lds, st, p);
+  OIBL_SET_MAX_LDS(KERN, lds);
+  hipLaunchKernelGGL(KERN, dim3((unsigned)grid, (unsigned)ksplit), dim3(512), lds, st, p);
   OIBL_LAUNCH_CHECK();
   return OIBL_OK;
+}
+
+template <bool FILTER>
+static RingDistLaunch<PairRingParams> pair_ring_launch(int precision) {
+  return precision == OIBL_F16MX    ? launch_ring_dist<pairwise_ring_kernel<FILTER, RING_MX>, PairRingParams>
+         : precision == OIBL_BF16X3 ? launch_ring_dist<pairwise_ring_kernel<FILTER, RING_X3>, PairRingParams>
+                                    : launch_ring_dist<pairwise_ring_kernel<FILTER>, PairRingParams>;
 }
 }  // extern "C++"
 
@@ -1023,11 +830,32 @@ static int pairwise_prepare(const void* x, int x_st, int m, const void* y, int y
   return prepare_rows_st(y, y_st, n, d, precision, *yn, yc, yo, st);
 }
 
+// one launch of the ring kernel: dist[rows][ldd] = distances of `rows` operand rows at x to n operand rows at y
+static int pairwise_ring_launch(const void* x, const float* xn, int rows, const void* y, const float* yn, int n,
+                                int d, int precision, float* dist, size_t ldd, hipStream_t st) {
+  const size_t es = (size_t)opnd_es(precision);
+  PairRingParams q = {};
+  q.x = x;
+  q.y = y;
+  q.xn = xn;
+  q.yn = yn;
+  q.dist = dist;
+  q.ldd = ldd;
+  q.x_bytes = (unsigned)((size_t)rows * d * es);
+  q.y_bytes = (unsigned)((size_t)n * d * es);
+  q.y_row_bytes = (long)d * es;
+  q.y_stride = 1;
+  q.m = rows;
+  q.n = n;
+  q.d = d;
+  return pair_ring_launch<false>(precision)(q, st, 1, "pairwise");
+}
+
 // dist[m rows starting at row0][ldd] from prepared operands
 static int pairwise_launch(const void* xo, const void* yo, const float* xn, const float* yn, int row0,
-                           int rows, int m_all, int n, int d, int precision, float* dist, size_t ldd,
-                           hipStream_t st) {
+                           int rows, int n, int d, int precision, float* dist, size_t ldd, hipStream_t st) {
   const size_t es = oibl_elem_size(precision);
+  const char* const x0 = (const char*)xo + (size_t)row0 * d * es;
   if (precision == OIBL_F16MX) {
     // the ring kernel is the only f16mx implementation: panels of rows / columns keep every launch inside
     // the 32-bit buffer offsets of its operand loaders
@@ -1037,45 +865,17 @@ static int pairwise_launch(const void* xo, const void* yo, const float* xn, cons
     for (long r0 = 0; r0 < rows; r0 += panel)
       for (long c0 = 0; c0 < n; c0 += panel) {
         const int pr = (int)(rows - r0 < panel ? rows - r0 : panel), pc = (int)(n - c0 < panel ? n - c0 : panel);
-        PairRingParams q = {};
-        q.x = (const char*)xo + (size_t)(row0 + r0) * d * 4;
-        q.y = (const char*)yo + (size_t)c0 * d * 4;
-        q.xn = xn + row0 + r0;
-        q.yn = yn + c0;
-        q.dist = dist + (size_t)r0 * ldd + c0;
-        q.ldd = ldd;
-        q.x_bytes = (unsigned)((size_t)pr * d * 4);
-        q.y_bytes = (unsigned)((size_t)pc * d * 4);
-        q.y_row_bytes = (long)d * 4;
-        q.yn_stride = 1;
-        q.m = pr;
-        q.n = pc;
-        q.d = d;
-        const int rc = launch_pairwise_ring<false, RING_MX>(q, st);
+        const int rc = pairwise_ring_launch(x0 + (size_t)r0 * d * 4, xn + row0 + r0, pr,
+                                            (const char*)yo + (size_t)c0 * d * 4, yn + c0, pc, d, precision,
+                                            dist + (size_t)r0 * ldd + c0, ldd, st);
         if (rc) return rc;
       }
     return OIBL_OK;
   }
-  if (mfma16(precision) && pair_ring_wanted(rows, n, d, (int)es) && ldd <= ((size_t)1 << 24)) {
-    PairRingParams q = {};
-    q.x = (const char*)xo + (size_t)row0 * d * es;
-    q.y = yo;
-    q.xn = xn + row0;
-    q.yn = yn;
-    q.dist = dist;
-    q.ldd = ldd;
-    q.x_bytes = (unsigned)((size_t)rows * d * es);
-    q.y_bytes = (unsigned)((size_t)n * d * es);
-    q.y_row_bytes = (long)d * es;
-    q.yn_stride = 1;
-    q.m = rows;
-    q.n = n;
-    q.d = d;
-    return precision == OIBL_BF16X3 ? launch_pairwise_ring<false, RING_X3>(q, st)
-                                    : launch_pairwise_ring<false>(q, st);
-  }
+  if (mfma16(precision) && pair_ring_wanted(rows, n, d, (int)es) && ldd <= ((size_t)1 << 24))
+    return pairwise_ring_launch(x0, xn + row0, rows, yo, yn, n, d, precision, dist, ldd, st);
   PairParams p;
-  p.x = (const char*)xo + (size_t)row0 * d * es;
+  p.x = x0;
   p.y = yo;
   p.xn = xn + row0;
   p.yn = yn;
@@ -1085,7 +885,6 @@ static int pairwise_launch(const void* xo, const void* yo, const float* xn, cons
   p.n = n;
   p.d = d;
   p.tiles_n = (n + 127) / 128;
-  (void)m_all;
   const long grid = (long)((rows + 127) / 128) * p.tiles_n;
   OIBL_REQUIRE(grid <= 0x7fffffffL, "pairwise: grid too large");
   if (precision == OIBL_BF16) {
@@ -1137,7 +936,7 @@ int oibl_pairwise_sqdist_st(const void* x, int x_st, int m, const void* y, int y
   float *xn, *yn;
   int rc = pairwise_prepare(x, x_st, m, y, y_st, n, d, precision, (char*)ws, &xo, &yo, &xn, &yn, stream);
   if (rc) return rc;
-  return pairwise_launch(xo, yo, xn, yn, 0, m, m, n, d, precision, dist, ldd, (hipStream_t)stream);
+  return pairwise_launch(xo, yo, xn, yn, 0, m, n, d, precision, dist, ldd, (hipStream_t)stream);
 }
 int oibl_pairwise_sqdist(const float* x, int m, const float* y, int n, int d, int precision,
                          float* dist, size_t ldd, void* ws, size_t ws_bytes, void* stream) {
@@ -1232,6 +1031,55 @@ int oibl_sqdist_topk(const float* x, int m, const float* y, int n, int d, int k,
                              out_val, out_idx, overflow, ws, ws_bytes, stream);
 }
 
+// The two passes of a fused path over what every ring distance kernel takes (RingDistParams); q arrives with the
+// caller's own fields set and the counts at wsb + t.off_cnt zeroed:
+//   1. thresholds: k-th smallest distance to a strided sample of S gallery rows (two K-halves when t.ksplit == 2)
+//   2. the full contraction, keeping what the kernel's policy keeps against them -> q.cand_val / cand_idx / cand_cnt
+// es: bytes per operand element.
+extern "C++" {
+template <typename Params>
+static int ring_sample_then_filter(Params& q, RingDistLaunch<Params> sample_pass, RingDistLaunch<Params> filter_pass,
+                                   const char* who, const void* xo, const float* xn, int m, const void* yo,
+                                   const float* yn, int n, int d, size_t es, int k, int index_base, char* wsb,
+                                   const TopkPlan& t, hipStream_t st) {
+  float* sample = (float*)(wsb + t.off_sample);
+  float* sval = (float*)(wsb + t.off_sval);
+  int32_t* sidx = (int32_t*)(wsb + t.off_sidx);
+  const size_t half = align_up((size_t)m * t.S * sizeof(float), 256) / sizeof(float);
+  q.x = xo;
+  q.y = yo;
+  q.xn = xn;
+  q.yn = yn;
+  q.dist = sample;
+  q.ldd = (size_t)t.S;
+  q.x_bytes = (unsigned)((size_t)m * d * es);
+  q.y_bytes = (unsigned)((size_t)n * d * es);
+  q.y_row_bytes = (long)d * es * t.stride;
+  q.y_stride = t.stride;
+  q.m = m;
+  q.n = t.S;
+  q.d = d;
+  q.part_stride = t.ksplit == 2 ? half : 0;
+  int rc = sample_pass(q, st, t.ksplit, who);
+  if (rc) return rc;
+  launch_sample_kth(sample, t.ksplit == 2 ? sample + half : nullptr, m, t.S, k, sval, sidx, st);
+  OIBL_LAUNCH_CHECK();
+  q.part_stride = 0;
+  q.dist = nullptr;
+  q.y_row_bytes = (long)d * es;
+  q.y_stride = 1;
+  q.n = n;
+  q.thr = sval + (k - 1);
+  q.thr_stride = k;
+  q.cand_val = (float*)(wsb + t.off_cval);
+  q.cand_idx = (int32_t*)(wsb + t.off_cidx);
+  q.cand_cnt = (int*)(wsb + t.off_cnt);
+  q.cap = t.cap;
+  q.index_base = index_base;
+  return filter_pass(q, st, 1, who);
+}
+}  // extern "C++"
+
 // everything behind the norm / operand preparation: xo, yo are the rows the contraction reads
 // (bf16, (hi, lo) groups or fp32 by precision), xn, yn their fp32 squared norms
 static int sqdist_topk_core(const void* xo, const float* xn, int m, const void* yo, const float* yn,
@@ -1241,60 +1089,19 @@ static int sqdist_topk_core(const void* xo, const float* xn, int m, const void* 
   int rc;
   if (overflow) OIBL_HIP_CHECK(hipMemsetAsync(overflow, 0, sizeof(int32_t), st));
   if (t.fused && !exact) {
-    // 1. thresholds: k-th smallest distance to a strided sample of S gallery rows
-    float* sample = (float*)(wsb + t.off_sample);
-    float* sval = (float*)(wsb + t.off_sval);
-    int32_t* sidx = (int32_t*)(wsb + t.off_sidx);
-    PairRingParams q = {};
-    q.x = xo;
-    q.y = yo;
-    q.xn = xn;
-    q.yn = yn;
-    q.dist = sample;
-    q.ldd = (size_t)t.S;
-    const bool x3 = precision == OIBL_BF16X3, mx = precision == OIBL_F16MX;
-    const size_t es = (size_t)opnd_es(precision);
-    q.x_bytes = (unsigned)((size_t)m * d * es);
-    q.y_bytes = (unsigned)((size_t)n * d * es);
-    q.y_row_bytes = (long)d * es * t.stride;
-    q.yn_stride = t.stride;
-    q.m = m;
-    q.n = t.S;
-    q.d = d;
     int* cnt = (int*)(wsb + t.off_cnt);
     OIBL_HIP_CHECK(hipMemsetAsync(cnt, 0, (size_t)(m + 1) * sizeof(int), st));  // counts + the yn_max slot
-    const size_t half = align_up((size_t)m * t.S * sizeof(float), 256) / sizeof(float);
+    PairRingParams q = {};
     if (t.ksplit == 2) {
-      q.part_stride = half;
+      // the thresholds of a split sample get a slack: a bound on what fp32 accumulation in another order can move
+      // a distance (each of the two orders is within K' 2^-24 |x||y| of the exact dot product, K' = d products —
+      // 3 d in bf16x3 — so they differ by at most twice that, and a distance by twice that again)
       q.yn_max = (unsigned*)(cnt + m);
+      q.thr_slack = 4.0f * (float)d * (precision == OIBL_BF16 ? 1.0f : 3.0f) * 5.9604645e-8f;
     }
-    rc = mx   ? launch_pairwise_ring<false, RING_MX>(q, st, t.ksplit)
-         : x3 ? launch_pairwise_ring<false, RING_X3>(q, st, t.ksplit)
-              : launch_pairwise_ring<false>(q, st, t.ksplit);
-    if (rc) return rc;
-    launch_sample_kth(sample, t.ksplit == 2 ? sample + half : nullptr, m, t.S, k, sval, sidx, st);
-    OIBL_LAUNCH_CHECK();
-    // 2. the full contraction, keeping only distances <= threshold (+ the slack of a split sample:
-    //    a bound on what fp32 accumulation in another order can move a distance)
-    q.part_stride = 0;
-    // (each of the two orders is within K' 2^-24 |x||y| of the exact dot product, K' = d products —
-    //  3 d in bf16x3 — so they differ by at most twice that, and a distance by twice that again)
-    q.thr_slack = t.ksplit == 2 ? 4.0f * (float)d * ((x3 || mx) ? 3.0f : 1.0f) * 5.9604645e-8f : 0.f;
-    q.dist = nullptr;
-    q.y_row_bytes = (long)d * es;
-    q.yn_stride = 1;
-    q.n = n;
-    q.thr = sval + (k - 1);
-    q.thr_stride = k;
-    q.cand_val = (float*)(wsb + t.off_cval);
-    q.cand_idx = (int32_t*)(wsb + t.off_cidx);
-    q.cand_cnt = cnt;
-    q.cap = t.cap;
-    q.index_base = index_base;
-    q.index_stride = 1;
-    rc = mx   ? launch_pairwise_ring<true, RING_MX>(q, st)
-         : x3 ? launch_pairwise_ring<true, RING_X3>(q, st)
-              : launch_pairwise_ring<true>(q, st);
+    // 1., 2. thresholds from a sample of the gallery, then the full contraction keeping only distances <= threshold
+    rc = ring_sample_then_filter(q, pair_ring_launch<false>(precision), pair_ring_launch<true>(precision), "pairwise",
+                                 xo, xn, m, yo, yn, n, d, (size_t)opnd_es(precision), k, index_base, wsb, t, st);
     if (rc) return rc;
     // 3. exact top-k of every candidate list ((value, index) keys: independent of append order)
     launch_row_topk(q.cand_val, q.cand_idx, m, t.cap, (size_t)t.cap, k, 0, out_val, out_idx, cnt,
@@ -1305,7 +1112,7 @@ static int sqdist_topk_core(const void* xo, const float* xn, int m, const void* 
   float* tile = (float*)(wsb + t.off_chunk);
   for (int r0 = 0; r0 < m; r0 += t.chunk) {
     const int rows = m - r0 < t.chunk ? m - r0 : t.chunk;
-    rc = pairwise_launch(xo, yo, xn, yn, r0, rows, m, n, d, precision, tile, (size_t)n, st);
+    rc = pairwise_launch(xo, yo, xn, yn, r0, rows, n, d, precision, tile, (size_t)n, st);
     if (rc) return rc;
     launch_row_topk(tile, nullptr, rows, n, (size_t)n, k, index_base, out_val + (size_t)r0 * k,
                     out_idx + (size_t)r0 * k, nullptr, nullptr, st);
@@ -1462,23 +1269,6 @@ size_t oibl_sqdist_topk_f16r_workspace_bytes(int m, int n, int d, int k) {
   return oibl_sqdist_topk_f16r_st_workspace_bytes(m, n, d, k, OIBL_ST_F32, OIBL_ST_F32);
 }
 
-extern "C++" {
-template <bool FILTER>
-static int launch_pairwise_f16r(F16rParams& p, hipStream_t st, int ksplit = 1) {
-  p.tiles_m = (p.m + 255) / 256;
-  p.tiles_n = (p.n + 255) / 256;
-  p.group_m = g_match_group;
-  const long grid = (long)p.tiles_m * p.tiles_n;
-  OIBL_REQUIRE(grid > 0 && grid <= 0x7fffffffL, "sqdist_topk_f16r: grid out of range");
-  constexpr int lds = RingGeo<2>::MAIN_LDS;
-  auto kern = pairwise_f16r_kernel<FILTER>;
-  OIBL_SET_MAX_LDS(kern, lds);
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid, (unsigned)ksplit), dim3(512), lds, st, p);
-  OIBL_LAUNCH_CHECK();
-  return OIBL_OK;
-}
-}  // extern "C++"
-
 // K2 of a k (the member slots per query) and whether (m, n, d, k) takes the fused path — what a caller that runs the
 // two stages itself (sharded matching: the rescoring behind the exchange of the filter lists) has to know
 int oibl_f16r_members(int k) { return k >= 1 ? f16r_k2(k) : 0; }
@@ -1511,52 +1301,20 @@ int oibl_f16r_filter_select(const void* xh, const float* xaux, const float* xn, 
   hipStream_t st = (hipStream_t)stream;
   const TopkPlan& t = f.t;
   if (overflow) OIBL_HIP_CHECK(hipMemsetAsync(overflow, 0, sizeof(int32_t), st));
-  float* sample = (float*)(wsb + t.off_sample);
-  float* sval = (float*)(wsb + t.off_sval);
-  int32_t* sidx = (int32_t*)(wsb + t.off_sidx);
   int* cnt = (int*)(wsb + t.off_cnt);
   unsigned* ymax = (unsigned*)(wsb + f.off_ymax);
   OIBL_HIP_CHECK(hipMemsetAsync(cnt, 0, (size_t)(m + 1) * sizeof(int), st));
   OIBL_HIP_CHECK(hipMemsetAsync(ymax, 0, 16, st));
-  // 1. thresholds: k-th smallest filter distance to a strided sample of S gallery rows
   F16rParams q = {};
-  q.x = xh;
-  q.y = yh;
-  q.xn = xn;
-  q.yn = yn;
   q.xaux = (const float4*)xaux;
   q.yaux = (const float4*)yaux;
-  q.dist = sample;
-  q.ldd = (size_t)t.S;
-  q.x_bytes = (unsigned)((size_t)m * d * 2);
-  q.y_bytes = (unsigned)((size_t)n * d * 2);
-  q.y_row_bytes = (long)d * 2 * t.stride;
-  q.y_stride = t.stride;
-  q.m = m;
-  q.n = t.S;
-  q.d = d;
   q.ymax = ymax;
   q.gamma = (float)d * 5.9604645e-8f;
-  const size_t half = align_up((size_t)m * t.S * sizeof(float), 256) / sizeof(float);
-  if (t.ksplit == 2) q.part_stride = half;
-  rc = launch_pairwise_f16r<false>(q, st, t.ksplit);
-  if (rc) return rc;
-  launch_sample_kth(sample, t.ksplit == 2 ? sample + half : nullptr, m, t.S, k, sval, sidx, st);
-  OIBL_LAUNCH_CHECK();
-  // 2. the full contraction, keeping the pairs whose filter distance could belong to a member of the true top-k
-  q.part_stride = 0;
-  q.dist = nullptr;
-  q.y_row_bytes = (long)d * 2;
-  q.y_stride = 1;
-  q.n = n;
-  q.thr = sval + (k - 1);
-  q.thr_stride = k;
-  q.cand_val = (float*)(wsb + t.off_cval);
-  q.cand_idx = (int32_t*)(wsb + t.off_cidx);
-  q.cand_cnt = cnt;
-  q.cap = t.cap;
-  q.index_base = index_base;
-  rc = launch_pairwise_f16r<true>(q, st);
+  // 1., 2. thresholds: k-th smallest filter distance to a strided sample of S gallery rows; then the full
+  //    contraction, keeping the pairs whose filter distance could belong to a member of the true top-k
+  rc = ring_sample_then_filter(q, launch_ring_dist<pairwise_f16r_kernel<false>, F16rParams>,
+                               launch_ring_dist<pairwise_f16r_kernel<true>, F16rParams>, "sqdist_topk_f16r", xh, xn, m,
+                               yh, yn, n, d, 2, k, index_base, wsb, t, st);
   if (rc) return rc;
   // 3. the members of every query's rescore set (a list beyond the window / capacity, or more than K2 members,
   //    raises *overflow)

@@ -41,30 +41,14 @@
 // oracle than the fp32 MFMA mode itself — and nothing about them depends on the fp16 pass except their cost.
 #pragma once
 
-#include "ring_core.h"
+#include "match_ring.h"
 
 namespace oibl {
 
-struct F16rParams {
-  const void* x;          // [m][d] fp16, scaled rows
-  const void* y;          // gallery rows at y_row_bytes
-  const float* xn;        // fp32 squared norms (of the fp32 rows)
-  const float* yn;        // yn[col * y_stride]
+// x: [m][d] fp16, scaled rows; xn, yn: the fp32 squared norms of the fp32 rows
+struct F16rParams : RingDistParams {
   const float4* xaux;     // {2^-e, |x| (rounded up), |residual| (rounded up), 0}
   const float4* yaux;     // yaux[col * y_stride]
-  float* dist;            // !FILTER: [m][ldd]
-  size_t ldd;
-  unsigned x_bytes, y_bytes;
-  long y_row_bytes;
-  int y_stride;
-  int m, n, d, tiles_m, tiles_n, group_m;
-  const float* thr;       // FILTER: thr[row * thr_stride]
-  int thr_stride;
-  float* cand_val;
-  int32_t* cand_idx;
-  int* cand_cnt;
-  int cap, index_base;
-  size_t part_stride;     // 2-way split-K of the sample pass (gridDim.y = 2): half h writes dist + h * part_stride
   unsigned* ymax;         // [4] bit patterns of max |y|, max |ry|: [0], [1] over the SAMPLE columns — written
                           // (atomicMax) by the !FILTER launch, read by the FILTER launch; [2], [3] over ALL gallery
                           // columns — written by the FILTER launch, read by the rescoring
@@ -132,88 +116,41 @@ __global__ __launch_bounds__(256) void f16r_prepare_kernel(const void* __restric
   }
 }
 
-// The ring distance kernel on fp16 rows (RING_F16: the bf16 stream with v_mfma_f32_32x32x16_f16), tile order and
-// main loop exactly pairwise_ring_kernel's; the epilogue undoes the row scales and, with FILTER, widens every
-// row's threshold by the pair's error bound.
-template <bool FILTER>
-__global__ __launch_bounds__(512) void pairwise_f16r_kernel(F16rParams p) {
-  using G = RingGeo<2>;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int wm = wave / G::WN, wn = wave % G::WN;
-  const unsigned id = xcd_remap(blockIdx.x, gridDim.x);
-  const unsigned gm = (unsigned)p.group_m;
-  const unsigned width = gm * (unsigned)p.tiles_n;
-  const unsigned grp = id / width, in_grp = id - grp * width;
-  const unsigned first_m = grp * gm;
-  const unsigned gsz = (unsigned)p.tiles_m - first_m < gm ? (unsigned)p.tiles_m - first_m : gm;
-  const int tm = (int)(first_m + in_grp % gsz), tn = (int)(in_grp / gsz);
-  const int m0 = tm * G::BM, n0 = tn * G::BN;
-
-  const int piece = ring_piece(wave, lane);
-  int rows_a[4], rows_b[4];
-#pragma unroll
-  for (int h = 0; h < 2; ++h)
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      rows_a[2 * h + i] = ring_a_row<2>(wave, lane, h, i);
-      rows_b[2 * h + i] = ring_b_row<2>(wave, lane, h, i);
-    }
-  const int ksplit = (int)gridDim.y, kh = (int)blockIdx.y;
-  const int d_part = p.d / ksplit;
-  const unsigned koff = (unsigned)kh * (unsigned)d_part * 2u;
-  RingRowLoader<2> la, lb;
-  la.init(static_cast<const char*>(p.x) + koff, p.x_bytes - koff, m0, p.m, (long)p.d * 2, rows_a, piece);
-  lb.init(static_cast<const char*>(p.y) + koff, p.y_bytes - koff, n0, p.n, p.y_row_bytes, rows_b, piece);
-
-  f32x16_t acc[4][2];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-  // one copy of the loop per stagger group (ring_core.h)
-  if ((wave >> 2) == 0) ring_mainloop<2, false, false, RING_F16, 0>(acc, smem, wave, lane, la, lb, d_part >> 6);
-  else ring_mainloop<2, false, false, RING_F16, 1>(acc, smem, wave, lane, la, lb, d_part >> 6);
-
-  float* const xn_s = reinterpret_cast<float*>(smem);   // 256 floats each
-  float* const yn_s = xn_s + 256;
-  float* const th_s = xn_s + 512;
-  float* const xs_s = xn_s + 768;     // -2 * 2^-ex
-  float* const xa_s = xn_s + 1024;    // A_i
-  float* const xb_s = xn_s + 1280;    // B_i
-  float* const ys_s = xn_s + 1536;    // 2^-ey
-  float* const yy_s = xn_s + 1792;    // |y_j|
-  float* const yr_s = xn_s + 2048;    // |ry_j|
-  if (threadIdx.x < 256) {
-    int r = m0 + (int)threadIdx.x;
-    if (r > p.m - 1) r = p.m - 1;
-    const float xn = p.xn[r];
+// The ring distance kernel on fp16 rows (RING_F16: the bf16 stream with v_mfma_f32_32x32x16_f16): ring_dist_tile
+// (match_ring.h) with the policy below — the epilogue undoes the row scales and, with FILTER, widens every row's
+// threshold by the pair's error bound.
+struct F16rPolicy {
+  using Params = F16rParams;
+  static constexpr int P = RING_F16, ES = 2, LIST_OFF = 12288;
+  // LDS next to the norms and thresholds, 256 floats each: -2 * 2^-ex, A_i, B_i of the rows; 2^-ey, |y_j|, |ry_j|
+  // of the columns
+  static constexpr int XS_S = 768, XA_S = 1024, XB_S = 1280, YS_S = 1536, YY_S = 1792, YR_S = 2048;
+  struct Col {
+    float yn, ys, yy, yr;
+  };
+  template <bool FILTER>
+  __device__ static __forceinline__ float stage_row(const Params& p, float* s, unsigned t, int r, float xn, float th) {
     const float4 a = p.xaux[r];
-    xn_s[threadIdx.x] = kh == 0 ? xn : 0.f;
-    xs_s[threadIdx.x] = -2.0f * a.x;
+    s[XS_S + t] = -2.0f * a.x;
     if (FILTER) {
       const float nx = a.y, rx = a.z;
       const float A = 2.0f * (rx + p.gamma * (nx + rx)), B = 2.0f * (nx + rx) * (1.0f + p.gamma);
       const float ymx = __uint_as_float(p.ymax[0]), rmx = __uint_as_float(p.ymax[1]);
-      xa_s[threadIdx.x] = A;
-      xb_s[threadIdx.x] = B;
+      s[XA_S + t] = A;
+      s[XB_S + t] = B;
       // sample k-th + the largest bound over the sample + the fp32 roundings of the two final distances
-      th_s[threadIdx.x] = p.thr[(long)r * p.thr_stride] + fmaf(A, ymx, B * rmx) + 1e-6f * (xn + ymx * ymx);
+      th = th + fmaf(A, ymx, B * rmx) + 1e-6f * (xn + ymx * ymx);
     }
-  } else {
-    int c = n0 + (int)threadIdx.x - 256;
-    if (c > p.n - 1) c = p.n - 1;
-    const float yn = p.yn[(long)c * p.y_stride];
-    const float4 a = p.yaux[(long)c * p.y_stride];
-    yn_s[threadIdx.x - 256] = kh == 0 ? yn : 0.f;
-    ys_s[threadIdx.x - 256] = a.x;
-    yy_s[threadIdx.x - 256] = a.y;
-    yr_s[threadIdx.x - 256] = a.z;
-    if (p.ymax && kh == 0 && tm == 0) {  // one column of tiles covers every column of the launch once
+    return th;
+  }
+  template <bool FILTER>
+  __device__ static __forceinline__ void stage_col(const Params& p, float* s, unsigned t, long ci, float, bool once,
+                                                   int lane) {
+    const float4 a = p.yaux[ci];
+    s[YS_S + t] = a.x;
+    s[YY_S + t] = a.y;
+    s[YR_S + t] = a.z;
+    if (p.ymax && once) {
       const float my = wave_max(a.y), mr = wave_max(a.z);   // (non-negative: bit patterns order as integers)
       if (lane == 0) {
         atomicMax(p.ymax + (FILTER ? 2 : 0), __float_as_uint(my));
@@ -221,88 +158,22 @@ __global__ __launch_bounds__(512) void pairwise_f16r_kernel(F16rParams p) {
       }
     }
   }
-  __syncthreads();
-  const int col0 = wn * 64 + (lane & 31), row0 = wm * 128 + 4 * (lane >> 5);
-  if constexpr (!FILTER) {
-    // (stores through one buffer descriptor per 32-row accumulator tile, scalar row offsets: pairwise_ring_kernel)
-    const float* const dbase = p.dist + (size_t)kh * p.part_stride + ((size_t)m0 + wm * 128) * p.ldd + n0;
-    const unsigned ldd4 = (unsigned)p.ldd * 4u;
-    const unsigned voff = (unsigned)(4 * (lane >> 5)) * ldd4 + (unsigned)col0 * 4u;
-    const int rows_left = p.m - m0 - row0;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const __amdgpu_buffer_rsrc_t rs_d = __builtin_amdgcn_make_buffer_rsrc(
-          const_cast<float*>(dbase + (size_t)(32 * i) * p.ldd), 0, 0x7fffffff, 0x00020000);
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const bool nok = n0 + col0 + 32 * j < p.n;
-        const float yn = yn_s[col0 + 32 * j], ys = ys_s[col0 + 32 * j];
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int rt = (r & 3) + 8 * (r >> 2), ro = 32 * i + rt;
-          const float dv = fmaf(acc[i][j][r] * ys, xs_s[row0 + ro], xn_s[row0 + ro] + yn);
-          if (nok && ro < rows_left)
-            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, dv), rs_d, (int)voff,
-                                                  (int)((unsigned)rt * ldd4 + 128u * j), 0);
-          if ((r & 7) == 7) __builtin_amdgcn_sched_barrier(0);
-        }
-      }
-    }
-  } else {
-    // per-lane survivor lists, then one round of atomics per tile (pairwise_ring_kernel, FILTER)
-    constexpr int LCAP = 8;
-    float* const l_val = reinterpret_cast<float*>(smem + 12288);
-    int* const l_idx = reinterpret_cast<int*>(smem + 12288 + LCAP * 512 * 4);
-    int* const l_row = reinterpret_cast<int*>(smem + 12288 + 2 * LCAP * 512 * 4);
-    const int rows_left = p.m - m0 - row0;
-    int nl = 0;
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int n = n0 + col0 + 32 * j;
-      const bool nok = n < p.n;
-      const float yn = yn_s[col0 + 32 * j], ys = ys_s[col0 + 32 * j];
-      const float yy = yy_s[col0 + 32 * j], yr = yr_s[col0 + 32 * j];
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int ro = 32 * i + (r & 3) + 8 * (r >> 2);
-          const float dv = fmaf(acc[i][j][r] * ys, xs_s[row0 + ro], xn_s[row0 + ro] + yn);
-          const float bound = th_s[row0 + ro] + fmaf(xa_s[row0 + ro], yy, xb_s[row0 + ro] * yr);
-          // !(dv > bound): a NaN on either side KEEPS the pair (the list then overflows into the exact path)
-          if (nok && ro < rows_left && !(dv > bound)) {
-            const int m = m0 + row0 + ro;
-            if (nl < LCAP) {
-              l_val[nl * 512 + threadIdx.x] = dv;
-              l_idx[nl * 512 + threadIdx.x] = p.index_base + n;
-              l_row[nl * 512 + threadIdx.x] = m;
-              ++nl;
-            } else {
-              const int pos = atomicAdd(p.cand_cnt + m, 1);
-              if (pos < p.cap) {
-                p.cand_val[(size_t)m * p.cap + pos] = dv;
-                p.cand_idx[(size_t)m * p.cap + pos] = p.index_base + n;
-              }
-            }
-          }
-        }
-    }
-    int e_row[LCAP], e_pos[LCAP];
-#pragma unroll
-    for (int e = 0; e < LCAP; ++e) {
-      e_row[e] = e < nl ? l_row[e * 512 + threadIdx.x] : 0;
-      e_pos[e] = p.cap;
-    }
-#pragma unroll
-    for (int e = 0; e < LCAP; ++e)
-      if (e < nl) e_pos[e] = atomicAdd(p.cand_cnt + e_row[e], 1);
-#pragma unroll
-    for (int e = 0; e < LCAP; ++e)
-      if (e < nl && e_pos[e] < p.cap) {
-        p.cand_val[(size_t)e_row[e] * p.cap + e_pos[e]] = l_val[e * 512 + threadIdx.x];
-        p.cand_idx[(size_t)e_row[e] * p.cap + e_pos[e]] = l_idx[e * 512 + threadIdx.x];
-      }
+  __device__ static __forceinline__ Col col(const float* s, int c) {
+    return {s[RING_YN_S + c], s[YS_S + c], s[YY_S + c], s[YR_S + c]};
   }
+  __device__ static __forceinline__ float dist(float acc, const float* s, int row, const Col& c) {
+    return fmaf(acc * c.ys, s[XS_S + row], s[RING_XN_S + row] + c.yn);
+  }
+  // !(dv > bound): a NaN on either side KEEPS the pair (the list then overflows into the exact path)
+  __device__ static __forceinline__ bool keep(float dv, const float* s, int row, const Col& c) {
+    const float bound = s[RING_TH_S + row] + fmaf(s[XA_S + row], c.yy, s[XB_S + row] * c.yr);
+    return !(dv > bound);
+  }
+};
+
+template <bool FILTER>
+__global__ __launch_bounds__(512) void pairwise_f16r_kernel(F16rParams p) {
+  ring_dist_tile<FILTER, F16rPolicy>(p);
 }
 
 // ---- selection: which candidates can belong to the true top-k ------------------------------------------------

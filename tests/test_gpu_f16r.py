@@ -134,6 +134,24 @@ def test_near_duplicate_gallery_overflows_into_the_exact_path(dev):
     assert torch.equal(i2, i) and torch.equal(v2, v)
 
 
+def test_identical_gallery_fills_the_lane_lists_and_the_capacity(dev):
+    """A gallery of one row repeated: every pair sits on its threshold, so every lane of the filter pass keeps all 128
+    distances of its tile — the per-lane lists (8 entries) fill and the rest claim their slots directly, and the
+    16384 candidates of a query outgrow the capacity (counted, not stored).  The flag is raised; the repeat on the
+    exact path returns the lists of the materialised fp32 matrix: ties towards the lowest index."""
+    m, n, d, k = 256, 16384, 256, 10
+    assert ops.f16r_fused(m, n, d, k)
+    x = synth.descriptors(m, d, seed=3).to(dev)
+    y = synth.descriptors(1, d, seed=4).repeat(n, 1).contiguous().to(dev)
+    _, _, flag = ops.sqdist_topk(x, y, k, precision="f16r", defer_check=True)
+    assert int(flag.item()) == 1
+    v, i = ops.sqdist_topk(x, y, k, precision="f16r")
+    want_v, want_i = ops.row_topk(ops.pairwise_sqdist(x, y, "fp32"), k)
+    assert torch.equal(i, want_i) and torch.equal(i.cpu(), torch.arange(k, dtype=torch.int32).repeat(m, 1))
+    # (the fp32 MFMA mode's own accumulation error, as in test_fused_lists_are_fp32_exact)
+    assert (v - want_v).abs().max() <= 1e-5 * max(1.0, float(want_v.abs().max()))
+
+
 @pytest.mark.parametrize("name", ["match_small", "match_nms"])
 def test_reference_rankings_and_recalls(name, dev):
     """The reference's own outputs (tests/golden, written by oracle/make_golden.py from ibl/evaluators.py): these
