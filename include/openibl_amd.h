@@ -275,6 +275,34 @@ int oibl_vgg16_conv5_forward_ev(const float* x_nchw, int N, int H, int W,
 int oibl_vgg16_pool4_forward(const float* x_nchw, int N, int H, int W, const void* const* packed_w_host,
                              const float* const* bias_host, int precision, float* pool4,
                              void* ws, size_t ws_bytes, void* stream);
+/* The frozen trunk for a cache of stored activations: the same pass, stopped at the same place, but conv4_3 + pool
+ * writes the STORED activation — exactly what conv5_1 reads inside oibl_vgg16_conv5_forward — straight into the
+ * caller's buffer lines [N][H/16][W/16][512] of the precision's element type (OIBL_BF16: 2-byte bf16; OIBL_BF16X3:
+ * split elements; OIBL_F16MX: f16mx lines INCLUDING the 1/8 storage scale; OIBL_F32: plain fp32), and nothing is
+ * launched behind it.  `lines` may be a 16-byte-aligned slice of a larger buffer.  Entries 0..9 of the pointer arrays
+ * are read; range flag (OIBL_F16MX) in the first word of the workspace; workspace from oibl_vgg16_workspace_bytes,
+ * or oibl_vgg16_u8_workspace_bytes for the _u8 variant (x_nhwc, mean3_host, std3_host as in
+ * oibl_vgg16_conv5_forward_u8).                                                                                    */
+int oibl_vgg16_pool4_lines_forward(const float* x_nchw, int N, int H, int W, const void* const* packed_w_host,
+                                   const float* const* bias_host, int precision, void* lines,
+                                   void* ws, size_t ws_bytes, void* stream);
+int oibl_vgg16_pool4_lines_forward_u8(const uint8_t* x_nhwc, int N, int H, int W, const float* mean3_host,
+                                      const float* std3_host, const void* const* packed_w_host,
+                                      const float* const* bias_host, int precision, void* lines,
+                                      void* ws, size_t ws_bytes, void* stream);
+/* conv5_1 .. conv5_3 on such lines [N][h][w][512] (h = H/16, w = W/16 of the images): the three layers are launched
+ * exactly as oibl_vgg16_conv5_forward launches them for a batch of the same N, H, W — the same kernels and the same
+ * split-K plans, which depend on N, h, w and the precision alone — so `feat` [N][h][w][512] (bf16 in OIBL_BF16,
+ * plain fp32 otherwise) is BIT-EQUAL to the whole forward's.  Only entries 10..12 of the two pointer arrays (13
+ * entries, as above) are read.  OIBL_F16MX: the first word of the workspace is the range flag, zeroed when the call
+ * starts and raised by these three layers; the 1/8 storage scale of the lines is undone in the layer that writes
+ * `feat`.  `lines` is only read.  Arguments are validated before any HIP call: OIBL_E_INVALID for null pointers, N,
+ * h or w < 1 and an unknown precision, OIBL_E_WORKSPACE for a short workspace.  The query returns 0 for an empty
+ * problem or an unknown precision.                                                                                 */
+size_t oibl_vgg16_conv5_from_pool4_workspace_bytes(int N, int h, int w, int precision);
+int oibl_vgg16_conv5_from_pool4(const void* lines, int N, int h, int w, const void* const* packed_w_host,
+                                const float* const* bias_host, int precision, void* feat,
+                                void* ws, size_t ws_bytes, void* stream);
 
 /* ---- NetVLAD + intra-norm + L2 ---------------------------------------------------- *
  * Replaces NetVLAD.forward (ibl/models/netvlad.py:44-61) and the normalisation that

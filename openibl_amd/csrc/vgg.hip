@@ -208,7 +208,8 @@ int oibl_vgg16_conv5_forward(const float* x_nchw, int N, int H, int W,
 static int vgg_forward_impl(const void* x, int u8, const float* mean3, const float* std3, int N, int H,
                             int W, const void* const* packed_w_host, const float* const* bias_host,
                             int precision, void* feat, void* ws, size_t ws_bytes, void* stream,
-                            void* ev_igemm_begin, void* ev_igemm_end, int last_layer = OIBL_VGG16_NUM_CONV - 1) {
+                            void* ev_igemm_begin, void* ev_igemm_end, int last_layer = OIBL_VGG16_NUM_CONV - 1,
+                            int stored_out = 0) {
   OIBL_REQUIRE(x && packed_w_host && bias_host && feat && ws, "vgg16: null pointer");
   OIBL_REQUIRE(!u8 || (mean3 && std3), "vgg16: uint8 input needs the mean / std constants");
   OIBL_REQUIRE(precision_ok(precision), "vgg16: bad precision %d", precision);
@@ -309,9 +310,10 @@ static int vgg_forward_impl(const void* x, int u8, const float* mean3, const flo
   for (int l = l0; l <= last_layer; ++l) {
     // bf16x3 / f16mx: the last layer hands the head a plain fp32 map
     const bool last = l == OIBL_VGG16_NUM_CONV - 1;
-    // (a pass that stops at an earlier layer writes `feat` itself only in fp32; the other formats are converted
-    //  behind the loop)
-    void* dst = (last || (l == last_layer && precision == OIBL_F32)) ? feat : (l % 2 == 0 ? (void*)bufA : (void*)bufB);
+    // (a pass that stops at an earlier layer writes `feat` itself in fp32, or — stored_out — when the caller wants the
+    //  stored activation as the next layer would read it; otherwise the other formats are converted behind the loop)
+    void* dst = (last || (l == last_layer && (precision == OIBL_F32 || stored_out))) ? feat
+                                                                                    : (l % 2 == 0 ? (void*)bufA : (void*)bufB);
     rc = conv3x3_impl(cur, N, h, w, kVgg[l].cin, packed_w_host[l], bias_host[l], kVgg[l].cout,
                       kVgg[l].relu, kVgg[l].pool, precision, dst, st, last, splitk, range_flag, act_scale,
                       last ? 1.f / act_scale : 1.f);
@@ -322,7 +324,7 @@ static int vgg_forward_impl(const void* x, int u8, const float* mean3, const flo
     }
     cur = dst;
   }
-  if (last_layer != OIBL_VGG16_NUM_CONV - 1 && precision != OIBL_F32) {
+  if (last_layer != OIBL_VGG16_NUM_CONV - 1 && precision != OIBL_F32 && !stored_out) {
     // the stored activation -> plain fp32 in activation units (f16mx: what the next layer would read, hi + q6(lo),
     // times the inverse of the storage scale)
     const size_t n = (size_t)N * h * w * kVgg[last_layer].cout;
@@ -347,6 +349,82 @@ int oibl_vgg16_pool4_forward(const float* x_nchw, int N, int H, int W, const voi
   // conv1_1 .. conv4_3 + pool: layers 0 .. 9 of the table
   return vgg_forward_impl(x_nchw, 0, nullptr, nullptr, N, H, W, packed_w_host, bias_host, precision, pool4, ws,
                           ws_bytes, stream, nullptr, nullptr, 9);
+}
+
+// the same pass with layer 9 writing the caller's buffer in the precision's element type: nothing is launched behind it
+int oibl_vgg16_pool4_lines_forward(const float* x_nchw, int N, int H, int W, const void* const* packed_w_host,
+                                   const float* const* bias_host, int precision, void* lines, void* ws,
+                                   size_t ws_bytes, void* stream) {
+  return vgg_forward_impl(x_nchw, 0, nullptr, nullptr, N, H, W, packed_w_host, bias_host, precision, lines, ws,
+                          ws_bytes, stream, nullptr, nullptr, 9, 1);
+}
+
+int oibl_vgg16_pool4_lines_forward_u8(const uint8_t* x_nhwc, int N, int H, int W, const float* mean3_host,
+                                      const float* std3_host, const void* const* packed_w_host,
+                                      const float* const* bias_host, int precision, void* lines, void* ws,
+                                      size_t ws_bytes, void* stream) {
+  return vgg_forward_impl(x_nhwc, 1, mean3_host, std3_host, N, H, W, packed_w_host, bias_host, precision, lines, ws,
+                          ws_bytes, stream, nullptr, nullptr, 9, 1);
+}
+
+// conv5_1 .. conv5_3 (layers 10 .. 12 of the table) on a stored pool4 activation: the tail of vgg_forward_impl's loop.
+// The three layers see the N, h, w they see there, and conv3x3_impl plans a layer from those alone (tile counts, the
+// split-K factor, mx_split_plan), so the launches — and the bits of `feat` — are the whole forward's.
+static size_t conv5_splitk_bytes(int N, int h, int w, int precision) {
+  size_t mx = 0;
+  for (int l = 10; l < OIBL_VGG16_NUM_CONV; ++l) {
+    const size_t b = conv_layer_scratch_bytes(N, h, w, kVgg[l].cin, kVgg[l].cout, kVgg[l].pool, precision);
+    mx = b > mx ? b : mx;
+  }
+  return mx;
+}
+
+size_t oibl_vgg16_conv5_from_pool4_workspace_bytes(int N, int h, int w, int precision) {
+  if (N <= 0 || h < 1 || w < 1 || !precision_ok(precision)) return 0;
+  const size_t act = align_up((size_t)N * h * w * 512 * oibl_elem_size(precision), 256);
+  return VGG_WS_HEAD + 2 * act + conv5_splitk_bytes(N, h, w, precision);
+}
+
+int oibl_vgg16_conv5_from_pool4(const void* lines, int N, int h, int w, const void* const* packed_w_host,
+                                const float* const* bias_host, int precision, void* feat, void* ws, size_t ws_bytes,
+                                void* stream) {
+  OIBL_REQUIRE(lines && packed_w_host && bias_host && feat && ws, "vgg16_conv5_from_pool4: null pointer");
+  OIBL_REQUIRE(precision_ok(precision), "vgg16_conv5_from_pool4: bad precision %d", precision);
+  OIBL_REQUIRE(N > 0 && h >= 1 && w >= 1, "vgg16_conv5_from_pool4: bad shape N=%d h=%d w=%d", N, h, w);
+  OIBL_REQUIRE((long)N * h * w < 0x7fffffffL, "vgg16_conv5_from_pool4: N*h*w must be < 2^31 (split the batch)");
+  for (int l = 10; l < OIBL_VGG16_NUM_CONV; ++l)
+    OIBL_REQUIRE(packed_w_host[l] && bias_host[l], "vgg16_conv5_from_pool4: null pointer (layer %d)", l);
+  OIBL_REQUIRE((uintptr_t)ws % 256 == 0, "vgg16_conv5_from_pool4: workspace must be 256-byte aligned");
+  const size_t need = oibl_vgg16_conv5_from_pool4_workspace_bytes(N, h, w, precision);
+  if (ws_bytes < need) {
+    set_error("vgg16_conv5_from_pool4: workspace %zu < required %zu bytes", ws_bytes, need);
+    return OIBL_E_WORKSPACE;
+  }
+  const size_t act = align_up((size_t)N * h * w * 512 * oibl_elem_size(precision), 256);
+  char* bufA = (char*)ws + VGG_WS_HEAD;
+  char* bufB = bufA + act;
+  char* splitk = conv5_splitk_bytes(N, h, w, precision) ? bufB + act : nullptr;
+  hipStream_t st = (hipStream_t)stream;
+  const bool mx = precision == OIBL_F16MX;
+  unsigned* const range_flag = mx ? (unsigned*)ws : nullptr;
+  int rc;
+  if (range_flag) {
+    rc = launch_clear_word(range_flag, st);
+    if (rc) return rc;
+  }
+  // f16mx: the lines hold the activation times the storage scale, as the whole forward's layers hand it on
+  const float act_scale = mx ? ldexpf(1.f, -g_mx_act_shift) : 1.f;
+  const void* cur = lines;
+  for (int l = 10; l < OIBL_VGG16_NUM_CONV; ++l) {
+    const bool last = l == OIBL_VGG16_NUM_CONV - 1;
+    void* dst = last ? feat : (l % 2 == 0 ? (void*)bufA : (void*)bufB);
+    rc = conv3x3_impl(cur, N, h, w, kVgg[l].cin, packed_w_host[l], bias_host[l], kVgg[l].cout, kVgg[l].relu,
+                      kVgg[l].pool, precision, dst, st, last, splitk, range_flag, act_scale,
+                      last ? 1.f / act_scale : 1.f);
+    if (rc) return rc;
+    cur = dst;
+  }
+  return OIBL_OK;
 }
 
 int oibl_vgg16_conv5_forward_ev(const float* x_nchw, int N, int H, int W,

@@ -141,15 +141,26 @@ def _gather_all(local: torch.Tensor, sync_gather: bool, rank: int, world: int) -
 
 
 def extract_features(model, data_loader, dataset, print_freq=10, vlad=True, pca=None, gpu=None,
-                     sync_gather=False, scales=None, store_dtype=None, use_graphs=True):
+                     sync_gather=False, scales=None, store_dtype=None, use_graphs=True, trunk_cache=None):
     """OrderedDict fname -> CPU descriptor for every item of `dataset` (evaluators.py:36-103).
     `use_graphs=False`: the two-lane route without hipGraph capture (loaders whose batch shapes rarely
     repeat; `openibl_amd.extract.MAX_CACHED_SHAPES` bounds the captured shapes kept otherwise).
 
     Each rank extracts the slice its DistributedSliceSampler yields; slices are gathered
-    rank-major and truncated to len(dataset) (the wrap-around padding of the last slices)."""
+    rank-major and truncated to len(dataset) (the wrap-around padding of the last slices).
+
+    trunk_cache: an `openibl_amd.trunk_cache.TrunkCache` filled from `data_loader` over `dataset` with the trunk
+    frozen: the descriptors come from its stored pool4 maps (the same bits), `data_loader` is not iterated.  Single
+    rank, one scale."""
     rank, world = _rank_world()
-    local = _extract_local(model, data_loader, vlad, pca, gpu, print_freq, rank, scales, store_dtype, use_graphs)
+    if trunk_cache is not None:
+        if world != 1 or scales is not None:
+            raise RuntimeError(f"extract_features: a trunk cache serves a single rank (world size {world}) and "
+                               "single-scale extraction; use the ordinary flow (trunk_cache=None)")
+        trunk_cache.check(model, len(dataset))
+        local = trunk_cache.descriptors(model, vlad, store_dtype, pca)
+    else:
+        local = _extract_local(model, data_loader, vlad, pca, gpu, print_freq, rank, scales, store_dtype, use_graphs)
     allf = _gather_all(local, sync_gather, rank, world)[: len(dataset)]
     features = OrderedDict()
     for item, row in zip(dataset, allf):

@@ -46,6 +46,16 @@ SIGNATURES = {
     "oibl_vgg16_pool4_forward": (c_int, [c_void_p, c_int, c_int, c_int, C.POINTER(c_void_p),
                                          C.POINTER(c_void_p), c_int, c_void_p, c_void_p,
                                          c_size_t, c_void_p]),
+    "oibl_vgg16_pool4_lines_forward": (c_int, [c_void_p, c_int, c_int, c_int, C.POINTER(c_void_p),
+                                               C.POINTER(c_void_p), c_int, c_void_p, c_void_p,
+                                               c_size_t, c_void_p]),
+    "oibl_vgg16_pool4_lines_forward_u8": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
+                                                  C.POINTER(c_void_p), C.POINTER(c_void_p), c_int, c_void_p,
+                                                  c_void_p, c_size_t, c_void_p]),
+    "oibl_vgg16_conv5_from_pool4_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "oibl_vgg16_conv5_from_pool4": (c_int, [c_void_p, c_int, c_int, c_int, C.POINTER(c_void_p),
+                                            C.POINTER(c_void_p), c_int, c_void_p, c_void_p,
+                                            c_size_t, c_void_p]),
     "oibl_vgg16_u8_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "oibl_vgg16_conv5_forward_u8": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
                                             C.POINTER(c_void_p), C.POINTER(c_void_p), c_int, c_void_p,

@@ -458,6 +458,116 @@ def vgg16_pool4(x: torch.Tensor, weights: Sequence[torch.Tensor], biases: Sequen
     return out
 
 
+def vgg16_pool4_lines(x: torch.Tensor, weights: Sequence[torch.Tensor], biases: Sequence[torch.Tensor], precision,
+                      mean=REF_MEAN, std=REF_STD, return_flag: bool = False, out: Optional[torch.Tensor] = None):
+    """The frozen trunk for a cache (oibl_vgg16_pool4_lines_forward[_u8]): x [N][3][H][W] float32 (normalised) or
+    [N][H][W][3] uint8 (raw) -> the pooled conv4_3 map [N][H//16][W//16][512] AS IT IS STORED between the layers of
+    `vgg16_conv5`, in the precision's element type (bf16; int32 containers of bf16x3 split elements or of f16mx lines,
+    the latter with their 2^-3 storage scale; float32) — what `vgg16_conv5_from_pool4` reads.  conv1_1 .. conv4_3 +
+    pool run exactly as in `vgg16_conv5` (weights / biases as there; entries 0..9 are read).
+    out: optional preallocated map of that shape and type, e.g. a contiguous slice of a cache: written in place.
+    return_flag: also the pass's f16mx range flag, as `vgg16_conv5` returns it (None in the other precisions)."""
+    p = precision_code(precision)
+    if p == F16R:
+        raise ValueError("vgg16_pool4_lines: 'f16r' is a matching arithmetic, not a backbone precision")
+    dev = _need_cuda(x, *weights[:10], *biases[:10], out)
+    u8 = x.dtype == torch.uint8
+    if u8:
+        if x.dim() != 4 or x.shape[3] != 3:
+            raise ValueError("vgg16_pool4_lines: uint8 input must be [N][H][W][3]")
+        N, H, W, _ = map(int, x.shape)
+    else:
+        if x.dtype != torch.float32 or x.dim() != 4 or x.shape[1] != 3:
+            raise ValueError("vgg16_pool4_lines expects a float32 [N][3][H][W] or uint8 [N][H][W][3] tensor")
+        N, _, H, W = map(int, x.shape)
+    if len(weights) < 10 or len(biases) < 10:
+        raise ValueError("vgg16_pool4_lines needs the weights and biases of conv1_1 .. conv4_3")
+    h, w = vgg16_feature_hw(H, W)
+    lib = _lib.load()
+    ws_bytes = (lib.oibl_vgg16_u8_workspace_bytes if u8 else lib.oibl_vgg16_workspace_bytes)(N, H, W, p)
+    if ws_bytes == 0:
+        raise ValueError(f"vgg16_pool4_lines: unsupported input shape {tuple(x.shape)}")
+    ws = workspace(ws_bytes, dev, "vgg")
+    if out is not None:
+        if tuple(out.shape) != (N, h, w, 512) or out.dtype != _DTYPES[p]:
+            raise ValueError("vgg16_pool4_lines: `out` must be a contiguous [N][h][w][512] map of the precision's "
+                             "element type")
+        lines = out
+    else:
+        lines = torch.empty((N, h, w, 512), dtype=_DTYPES[p], device=dev)
+    wp = (C.c_void_p * 13)(*[t.data_ptr() for t in weights[:10]])
+    bp = (C.c_void_p * 13)(*[t.data_ptr() for t in biases[:10]])
+    if u8:
+        m3 = (C.c_float * 3)(*[float(v) for v in mean])
+        s3 = (C.c_float * 3)(*[float(v) for v in std])
+        _lib.check(lib.oibl_vgg16_pool4_lines_forward_u8(_ptr(x), N, H, W, m3, s3, wp, bp, p, _ptr(lines), _ptr(ws),
+                                                         ws.numel(), _stream(dev)), "vgg16_pool4_lines_forward_u8")
+    else:
+        _lib.check(lib.oibl_vgg16_pool4_lines_forward(_ptr(x), N, H, W, wp, bp, p, _ptr(lines), _ptr(ws),
+                                                      ws.numel(), _stream(dev)), "vgg16_pool4_lines_forward")
+    if return_flag:
+        return lines, (ws[:4].view(torch.int32) if p == F16MX else None)
+    return lines
+
+
+def widen_pool4_lines(lines: torch.Tensor, precision) -> torch.Tensor:
+    """Stored pool4 lines (`vgg16_pool4_lines`) -> plain float32 in activation units, what `vgg16_pool4` returns:
+    bf16 widened, bf16x3 hi + lo, f16mx hi + q6(lo) with the 2^-3 storage scale undone (exact)."""
+    p = precision_code(precision)
+    _need_cuda(lines)
+    if lines.dtype != _DTYPES.get(p):
+        raise ValueError("widen_pool4_lines: the lines are not of the precision's element type")
+    if p == F32:
+        return lines
+    if p == BF16:
+        return to_f32(lines)
+    if p == BF16X3:
+        return x3_join(lines)
+    return mx_join(lines).mul_(8.0)
+
+
+def vgg16_conv5_from_pool4(lines: torch.Tensor, weights: Sequence[torch.Tensor], biases: Sequence[torch.Tensor],
+                           precision, return_flag: bool = False, out: Optional[torch.Tensor] = None):
+    """conv5_1 .. conv5_3 on stored pool4 lines [N][h][w][512] (`vgg16_pool4_lines`, same precision) -> the conv5_3 map
+    [N][h][w][512] in the head's element type, bit-equal to `vgg16_conv5` on the images the lines came from in a batch
+    of the same N (oibl_vgg16_conv5_from_pool4: the whole forward's launches for these three layers).  weights /
+    biases: the 13 entries of `vgg16_conv5` (entries 10..12 are read) or just those three.  `lines` is only read.
+    out: optional preallocated [N][h][w][512] map of the head's element type (a contiguous slice of a larger map).
+    return_flag: also the f16mx range flag of these three layers, an int32 [1] view of the first word of this
+    stream's backbone workspace (None in the other precisions)."""
+    p = precision_code(precision)
+    if p == F16R:
+        raise ValueError("vgg16_conv5_from_pool4: 'f16r' is a matching arithmetic, not a backbone precision")
+    if len(weights) != len(biases) or len(weights) not in (3, 13):
+        raise ValueError("vgg16_conv5_from_pool4 needs the 13 weights and biases of the backbone or the 3 of conv5")
+    w3, b3 = list(weights[-3:]), list(biases[-3:])
+    dev = _need_cuda(lines, *w3, *b3, out)
+    if lines.dim() != 4 or int(lines.shape[3]) != 512 or lines.dtype != _DTYPES[p]:
+        raise ValueError("vgg16_conv5_from_pool4 expects [N][h][w][512] lines of the precision's element type")
+    if any(t.dtype != _DTYPES[p] or tuple(t.shape) != (9, 512, 512) for t in w3):
+        raise ValueError("vgg16_conv5_from_pool4: the conv5 weights must be packed [9][512][512] in the same precision")
+    N, h, w, _ = map(int, lines.shape)
+    lib = _lib.load()
+    ws_bytes = lib.oibl_vgg16_conv5_from_pool4_workspace_bytes(N, h, w, p)
+    if ws_bytes == 0:
+        raise ValueError(f"vgg16_conv5_from_pool4: unsupported shape {tuple(lines.shape)}")
+    ws = workspace(ws_bytes, dev, "vgg")
+    if out is not None:
+        if tuple(out.shape) != (N, h, w, 512) or out.dtype != _DTYPES[head_precision(p)]:
+            raise ValueError("vgg16_conv5_from_pool4: `out` must be a contiguous [N][h][w][512] map of the head's "
+                             "element type")
+        feat = out
+    else:
+        feat = torch.empty((N, h, w, 512), dtype=_DTYPES[head_precision(p)], device=dev)
+    wp = (C.c_void_p * 13)(*([None] * 10 + [t.data_ptr() for t in w3]))
+    bp = (C.c_void_p * 13)(*([None] * 10 + [t.data_ptr() for t in b3]))
+    _lib.check(lib.oibl_vgg16_conv5_from_pool4(_ptr(lines), N, h, w, wp, bp, p, _ptr(feat), _ptr(ws), ws.numel(),
+                                               _stream(dev)), "vgg16_conv5_from_pool4")
+    if return_flag:
+        return feat, (ws[:4].view(torch.int32) if p == F16MX else None)
+    return feat
+
+
 def global_maxpool_nhwc(feat: torch.Tensor) -> torch.Tensor:
     """[N][h][w][C] T -> [N][C] fp32 (AdaptiveMaxPool2d(1))."""
     dev = _need_cuda(feat)
