@@ -1994,6 +1994,13 @@ __global__ __launch_bounds__(1024) void vgg_stem_x3_kernel(StemParams p) {
   }
 }
 
+#include "stem_mx12.h"
+OIBL_HOOK(int, g_stem_mx12, 1);  // test hook: 0 = the float32-input f16mx stem on vgg_stem_x3_kernel<true> (A/B, bit comparisons)
+OIBL_HOOK(unsigned*, g_stem_mx_flag, nullptr);  // test hook: the range flag oibl_vgg16_stem_mx hands its kernel (the entry has none)
+#ifdef OIBL_DEBUG_HOOKS
+static int g_stem_mx_route = 0;  // the kernel the last float32-input f16mx stem launched: 12 or 16 (waves); 0 = none yet
+#endif
+
 // u8_mean3 / u8_std3 (host pointers, both or neither): x is the raw uint8 NHWC image and the kernel normalises
 // (vgg_stem_x3_kernel, U8)
 int launch_vgg_stem_x3(const void* x, int N, int H, int W, const float* w1, const float* b1, const void* packed_w2,
@@ -2038,10 +2045,19 @@ int launch_vgg_stem_x3(const void* x, int N, int H, int W, const float* w1, cons
     auto kern = vgg_stem_x3_kernel<true, true>;
     OIBL_SET_MAX_LDS(kern, S3_LDS_BYTES);
     hipLaunchKernelGGL(kern, gridmx, dim3(1024), S3_LDS_BYTES, st, p);
+  } else if (mx && g_stem_mx12) {
+    OIBL_SET_MAX_LDS(stem_mx12_kernel, S3_LDS_BYTES);
+    hipLaunchKernelGGL(stem_mx12_kernel, gridmx, dim3(64 * (4 + M12_PROD)), S3_LDS_BYTES, st, p);
+#ifdef OIBL_DEBUG_HOOKS
+    g_stem_mx_route = 12;
+#endif
   } else if (mx) {
     auto kern = vgg_stem_x3_kernel<true>;
     OIBL_SET_MAX_LDS(kern, S3_LDS_BYTES);
     hipLaunchKernelGGL(kern, gridmx, dim3(1024), S3_LDS_BYTES, st, p);
+#ifdef OIBL_DEBUG_HOOKS
+    g_stem_mx_route = 16;
+#endif
   } else if (u8) {
     auto kern = vgg_stem_x3_kernel<false, true>;
     OIBL_SET_MAX_LDS(kern, S3_LDS_BYTES);
@@ -2089,12 +2105,24 @@ int oibl_vgg16_stem_mx(const float* x_nchw, int N, int H, int W, const float* w1
   OIBL_REQUIRE(stem_eligible(N, H, W), "vgg16_stem_mx: input of %d x 3 x %d x %d exceeds 3.5 GB", N, H, W);
   OIBL_REQUIRE((uintptr_t)packed_w2 % 16 == 0 && (uintptr_t)out % 16 == 0 && (uintptr_t)x_nchw % 4 == 0,
                "vgg16_stem_mx: packed weights / output must be 16-byte aligned");
-  return launch_vgg_stem_x3(x_nchw, N, H, W, w1_oihw, b1, packed_w2, b2, out, (hipStream_t)stream, true);
+  return launch_vgg_stem_x3(x_nchw, N, H, W, w1_oihw, b1, packed_w2, b2, out, (hipStream_t)stream, true, g_stem_mx_flag);
 }
 
 #ifdef OIBL_DEBUG_HOOKS
 int oibl_debug_set_stem3_prio(int prio) {
   g_stem3_prio = prio < 0 ? 0 : (prio & 15);
+  return OIBL_OK;
+}
+
+int oibl_debug_set_stem_mx12(int on) {
+  g_stem_mx12 = on ? 1 : 0;
+  return OIBL_OK;
+}
+
+int oibl_debug_last_stem_mx_route(void) { return g_stem_mx_route; }
+
+int oibl_debug_set_stem_mx_flag(void* dev_u32) {
+  g_stem_mx_flag = (unsigned*)dev_u32;
   return OIBL_OK;
 }
 

@@ -216,6 +216,9 @@ _HOOKS = {"oibl_debug_set_regstage": (c_int, [c_int]),
           "oibl_debug_set_netvlad_slabs": (c_int, [c_int]),
           "oibl_debug_set_mx_splitk": (c_int, [c_int]),
           "oibl_debug_set_stem_u8": (c_int, [c_int]),
+          "oibl_debug_set_stem_mx12": (c_int, [c_int]),
+          "oibl_debug_set_stem_mx_flag": (c_int, [c_void_p]),
+          "oibl_debug_last_stem_mx_route": (c_int, []),
           "oibl_debug_set_prof_buffer": (c_int, [c_void_p])}
 
 ABI_VERSION = 3
@@ -241,7 +244,7 @@ _HOOK_DEFAULTS = {"oibl_debug_set_regstage": 0, "oibl_debug_set_conv11_valu": 0,
                   "oibl_debug_set_conv_korder": -1, "oibl_debug_set_mx_variant": 0, "oibl_debug_set_conv_splitk": 1,
                   "oibl_debug_set_stem3_prio": 0, "oibl_debug_set_match_group": 4, "oibl_debug_set_match_splitk": 1,
                   "oibl_debug_set_pca_small": 1, "oibl_debug_set_pca_stream": 1, "oibl_debug_set_mx_act_shift": 3, "oibl_debug_set_netvlad_slabs": 1,
-                  "oibl_debug_set_mx_splitk": 1, "oibl_debug_set_stem_u8": 1,
+                  "oibl_debug_set_mx_splitk": 1, "oibl_debug_set_stem_u8": 1, "oibl_debug_set_stem_mx12": 1, "oibl_debug_set_stem_mx_flag": None,
                   "oibl_debug_set_prof_buffer": None}
 
 
