@@ -11,7 +11,10 @@ What differs from the reference, and why:
     such call behind one argmax and one gather, not a Python loop over the tuples;
   * an unknown loss_type raises ValueError (the reference's `assert ("Unknown loss function")` never fires);
   * `vlad=False` (max-pooled features) raises NotImplementedError: pool_x carries no graph here;
-  * single rank: no gradient all-reduce is added (the reference leaves that to DistributedDataParallel).
+  * single rank: no gradient all-reduce is added (the reference leaves that to DistributedDataParallel);
+  * `augment` (extension, off by default): with an openibl_amd.augment.ColorJitter set, the loader delivers raw uint8
+    tuples (`get_transformer_train(..., as_uint8=True)`) and `_parse_data` jitters and normalises them on the device —
+    the reference's ColorJitter runs inside its host transform.
 The loop itself — meters, one `loss.item()` synchronisation per iteration, the printed line — is the reference's."""
 from __future__ import annotations
 
@@ -54,16 +57,31 @@ def _stack_tuples(inputs):
     return torch.stack([item[0] for item in inputs]).permute(1, 0, 2, 3, 4)
 
 
+def _augment_tuples(augment, imgs, gpu):
+    """imgs [B][N][H][W][3] uint8 on the host (the loader's raw tuples, `get_transformer_train(..., as_uint8=True)`)
+    -> [B][N][3][H][W] float32 on the device: the bytes cross as they are, and `augment` (an
+    openibl_amd.augment.ColorJitter: [n][H][W][3] uint8 -> [n][3][H][W] float32) jitters every image on its own."""
+    if imgs.dtype != torch.uint8 or imgs.dim() != 5 or imgs.shape[-1] != 3:
+        raise ValueError(f"a trainer with `augment` set takes uint8 tuples [B][N][H][W][3] from the loader "
+                         f"(get_transformer_train(..., as_uint8=True)), got {imgs.dtype} {tuple(imgs.shape)}")
+    B, N, H, W, _ = imgs.shape
+    out = augment(imgs.contiguous().cuda(gpu).view(B * N, H, W, 3))
+    return out.view(B, N, 3, H, W)
+
+
 class Trainer(object):
     """Training module for NetVLAD (CVPR'16, loss_type='triplet') and SARE (ICCV'19, loss_type='sare_ind' or
     'sare_joint').  `model` is an EmbedNet (possibly inside a `.module` container) on the device."""
 
-    def __init__(self, model, margin=0.3, gpu=None, temp=0.07):
+    def __init__(self, model, margin=0.3, gpu=None, temp=0.07, augment=None):
         super(Trainer, self).__init__()
         self.model = model
         self.gpu = gpu
         self.margin = margin
         self.temp = temp
+        # None: the loader delivers normalised float tuples (the reference's flow); an
+        # openibl_amd.augment.ColorJitter: it delivers raw uint8 tuples, jittered and normalised on the device
+        self.augment = augment
 
     def train(self, epoch, sub_id, data_loader, optimizer, train_iters,
               print_freq=1, vlad=True, loss_type='triplet'):
@@ -100,6 +118,8 @@ class Trainer(object):
 
     def _parse_data(self, inputs):
         # [B][tuple size][C][H][W]
+        if self.augment is not None:
+            return _augment_tuples(self.augment, _stack_tuples(inputs), self.gpu)
         return _stack_tuples(inputs).cuda(self.gpu)
 
     def _forward(self, inputs, vlad, loss_type):
@@ -128,10 +148,11 @@ class SFRSTrainer(object):
     the number of tuples per batch."""
 
     def __init__(self, model, model_cache, margin=0.3,
-                 neg_num=10, gpu=None, temp=[0.07, ]):
+                 neg_num=10, gpu=None, temp=[0.07, ], augment=None):
         super(SFRSTrainer, self).__init__()
         self.model = model
         self.model_cache = model_cache
+        self.augment = augment      # as Trainer.augment
 
         self.margin = margin
         self.gpu = gpu
@@ -180,6 +201,10 @@ class SFRSTrainer(object):
 
     def _parse_data(self, inputs):
         imgs = _stack_tuples(inputs)
+        if self.augment is not None:
+            # every image is jittered once, the anchor included: the easy and the difficult part share the anchor's
+            # jittered image, and the teacher and the student see the same inputs_diff, as in the reference
+            imgs = _augment_tuples(self.augment, imgs, self.gpu)
         # easy: anchor, positive, neg_num negatives; diff: anchor and the difficult positives behind them
         imgs_easy = imgs[:, :self.neg_num + 2]
         imgs_diff = torch.cat((imgs[:, :1], imgs[:, self.neg_num + 2:]), dim=1)

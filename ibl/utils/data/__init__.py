@@ -69,6 +69,12 @@ def get_transformer_test(height, width, tokyo=False, as_uint8=False):
     return _TestTransform(height, width, keep_aspect=tokyo, as_uint8=as_uint8)
 
 
-def get_transformer_train(height, width):
-    # colour jitter belongs to training, which this package does not implement
-    return _TestTransform(height, width)
+def get_transformer_train(height, width, as_uint8=False):
+    """The host half of the training transform.  The reference's is ColorJitter(0.7, 0.7, 0.7, 0.5), Resize,
+    ToTensor, Normalize on the host; here the colour jitter runs on the device (openibl_amd.augment.ColorJitter, the
+    `augment` of ibl.trainers), behind the resize.  as_uint8=True (extension): the resized raw [H][W][3] bytes, which
+    a trainer with `augment` set jitters and normalises on the device — the batch crosses PCIe as uint8.  The default
+    is the test transform, Resize + ToTensor + Normalize without jitter: what a trainer without `augment` takes.
+    (Jitter after the resize equals the reference's jitter before it bit for bit when the stored images already have
+    the target size; otherwise the two differ in rounding.)"""
+    return _TestTransform(height, width, as_uint8=as_uint8)

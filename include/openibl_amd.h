@@ -695,6 +695,35 @@ int oibl_mine_rows(const float* dist, int A, int G, size_t ld, const int32_t* cs
                    int32_t* cand_len, int32_t* cache_pos, int32_t* pos_ranked, float* pos_jac, void* ws,
                    size_t ws_bytes, void* stream);
 
+/* ---- training colour jitter on raw uint8 batches ------------------------------------------ *
+ * Replaces ColorJitter(0.7, 0.7, 0.7, 0.5) of get_transformer_train (ibl/utils/data/__init__.py:29-35; torchvision
+ * delegates to PIL's ImageEnhance.Brightness / Contrast / Color and to a hue shift through PIL's HSV mode) and,
+ * for out_kind OIBL_JITTER_F32_NCHW, the ToTensor + Normalize behind it.  The arithmetic is PIL's, rounding by
+ * rounding (csrc/augment.hip states it): the uint8 result equals PIL's bit for bit.
+ *   x_nhwc [N][H][W][3] uint8   the loader's raw images (any byte alignment; bases that are 4-byte aligned are
+ *                               read and written with whole dwords).
+ *   records [N] x 32 bytes      one record per image, eight 32-bit words:
+ *                                 words 0..3  int32 op codes in application order: 0 brightness, 1 contrast,
+ *                                             2 saturation, 3 hue, anything else (-1) skip; every op at most once
+ *                                             (a second contrast op in a record is skipped);
+ *                                 words 4..6  fp32 factors of brightness, contrast, saturation;
+ *                                 word  7     the hue shift added to the H byte, 0..255 (mod 256).  The hue op is
+ *                                             the HSV round trip even when the shift is 0 (it is lossy).
+ *                               NULL: no jitter — one launch, the plain copy / normalisation.
+ *   out_kind OIBL_JITTER_U8_NHWC   out [N][H][W][3] uint8, the jittered images; mean3_host / std3_host unused.
+ *            OIBL_JITTER_F32_NCHW  out [N][3][H][W] fp32 = (float(u8) / 255.0f - mean_c) / std_c, both divisions
+ *                               IEEE: the bits of the loader's host transform on the jittered bytes.
+ * Two launches: per-workgroup integer partial sums of the luma behind the ops ordered before contrast (images
+ * without a contrast op return at once), then the pass that finishes the sum, recomputes the prefix and applies
+ * everything.  Integer sums, no atomics: identical bits from run to run, and an image's result does not depend on
+ * the rest of the batch.  H * W <= 2^28.  Workspace: the partial sums (8 bytes each, at most 1024 per image). */
+#define OIBL_JITTER_U8_NHWC 0
+#define OIBL_JITTER_F32_NCHW 1
+size_t oibl_color_jitter_u8_workspace_bytes(int N, int H, int W);
+int oibl_color_jitter_u8(const uint8_t* x_nhwc, int N, int H, int W, const void* records, int out_kind,
+                         const float* mean3_host, const float* std3_host, void* out, void* ws, size_t ws_bytes,
+                         void* stream);
+
 /* ---- recall counting ---------------------------------------------------------------- *
  * Replaces the per-query Python loop of evaluate_all and spatial_nms
  * (ibl/evaluators.py:132-140, 149-160).  For every query, the rank (0-based, inside the

@@ -1,0 +1,114 @@
+"""Training augmentation on the device: `ColorJitter` for raw uint8 batches.
+
+The reference's training transform is ColorJitter(0.7, 0.7, 0.7, 0.5) -> Resize -> ToTensor -> Normalize
+(ibl/utils/data/__init__.py:29-35 of the reference, through torchvision and PIL on the host).  Here the loader hands
+over the resized raw bytes (`get_transformer_train(..., as_uint8=True)`), the batch crosses to the device as uint8 and
+one call of ops.color_jitter applies the jitter with PIL's arithmetic — bit for bit — and the normalisation behind it.
+
+Limit: the reference jitters BEFORE Resize, this flow after it.  The two agree bit for bit exactly when the stored
+images already have the target size (Pitts: 640 x 480); otherwise both are valid augmentations of the same
+distribution that differ in rounding."""
+from __future__ import annotations
+
+import numbers
+from typing import Optional
+
+import torch
+
+from . import ops
+
+BRIGHTNESS, CONTRAST, SATURATION, HUE, SKIP = 0, 1, 2, 3, -1
+
+
+def _check_range(value, name, center=1.0, bound=(0.0, float("inf")), clip_first_on_zero=True):
+    """torchvision's ColorJitter._check_input: a scalar v is [center - v, center + v] (the lower end clipped at 0 for
+    everything but hue), a pair is taken as given; a range that is the single point `center` disables the op."""
+    if isinstance(value, numbers.Number) and not isinstance(value, bool):
+        if value < 0:
+            raise ValueError(f"If {name} is a single number, it must be non negative.")
+        value = [center - float(value), center + float(value)]
+        if clip_first_on_zero:
+            value[0] = max(value[0], 0.0)
+    elif isinstance(value, (tuple, list)) and len(value) == 2:
+        value = [float(value[0]), float(value[1])]
+    else:
+        raise TypeError(f"{name} should be a single number or a list/tuple with length 2.")
+    if not bound[0] <= value[0] <= value[1] <= bound[1]:
+        raise ValueError(f"{name} values should be between {bound}, but got {value}.")
+    if value[0] == value[1] == center:
+        return None
+    return (value[0], value[1])
+
+
+def hue_byte(hue: float) -> int:
+    """What torchvision adds to PIL's H plane: uint8(hue * 255), truncated toward zero, wrapping mod 256."""
+    return int(hue * 255) % 256
+
+
+class ColorJitter(object):
+    """torchvision.transforms.ColorJitter for a raw uint8 batch on the device.
+
+    brightness, contrast, saturation: a scalar v (factor drawn from [max(0, 1 - v), 1 + v]) or a pair (lo, hi);
+    hue: a scalar v with 0 <= v <= 0.5 (shift drawn from [-v, v]) or a pair inside [-0.5, 0.5].  A range that
+    contains only the identity disables its op.  `generator`: the torch.Generator (CPU) the draws come from; None:
+    the global one.  `out`: 'float' (normalised [N][3][H][W] float32, what forward_train takes) or 'uint8'.
+
+    Every image of a batch gets its own order and factors.  The draws follow the current torchvision's
+    `ColorJitter.get_params` — one torch.randperm(4), then one torch.empty(1).uniform_(lo, hi) per ENABLED op in the
+    order brightness, contrast, saturation, hue.  torchvision is not available where this was written: the order
+    of the draws is taken from its published source and could not be verified against a run of it, so the same seed
+    is not guaranteed to give torchvision's stream; the distribution is the same either way."""
+
+    def __init__(self, brightness=0, contrast=0, saturation=0, hue=0, generator: Optional[torch.Generator] = None,
+                 out: str = "float"):
+        self.brightness = _check_range(brightness, "brightness")
+        self.contrast = _check_range(contrast, "contrast")
+        self.saturation = _check_range(saturation, "saturation")
+        self.hue = _check_range(hue, "hue", center=0.0, bound=(-0.5, 0.5), clip_first_on_zero=False)
+        if out not in ops.JITTER_OUT:
+            raise ValueError(f"ColorJitter: out must be 'float' or 'uint8', not {out!r}")
+        self.generator = generator
+        self.out = out
+        self.last_records = None    # the records of the last call (None: nothing was jittered)
+
+    @property
+    def enabled(self) -> bool:
+        return any(r is not None for r in (self.brightness, self.contrast, self.saturation, self.hue))
+
+    def _uniform(self, rng) -> float:
+        return float(torch.empty(1).uniform_(rng[0], rng[1], generator=self.generator))
+
+    def draw(self, n: int) -> torch.Tensor:
+        """The records of n images, on the host: int32 [n][8] (ops.color_jitter).  A disabled op never appears in a
+        record: its place in the drawn order holds -1."""
+        ranges = (self.brightness, self.contrast, self.saturation)
+        codes = torch.full((n, 4), SKIP, dtype=torch.int32)
+        factors = torch.ones((n, 3), dtype=torch.float32)
+        shifts = torch.zeros((n,), dtype=torch.int32)
+        for i in range(n):
+            order = torch.randperm(4, generator=self.generator).tolist()
+            for k, rng in enumerate(ranges):
+                if rng is not None:
+                    factors[i, k] = self._uniform(rng)
+            if self.hue is not None:
+                shifts[i] = hue_byte(self._uniform(self.hue))
+            for place, op in enumerate(order):
+                if (self.hue if op == HUE else ranges[op]) is not None:
+                    codes[i, place] = op
+        return torch.cat((codes, factors.view(torch.int32), shifts[:, None]), dim=1).contiguous()
+
+    def __call__(self, u8_batch: torch.Tensor, records: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """u8_batch [N][H][W][3] uint8 on the device -> the jittered batch (`out`).  `records`: host or device
+        records to use instead of drawing (a replay).  With every op disabled nothing but the plain normalisation
+        (or copy) is launched."""
+        if records is None:
+            if not self.enabled:
+                self.last_records = None
+                return ops.color_jitter(u8_batch, None, out=self.out)
+            records = self.draw(u8_batch.shape[0])
+        self.last_records = records
+        return ops.color_jitter(u8_batch, records.to(u8_batch.device), out=self.out)
+
+    def __repr__(self):
+        return (f"{self.__class__.__name__}(brightness={self.brightness}, contrast={self.contrast}, "
+                f"saturation={self.saturation}, hue={self.hue})")

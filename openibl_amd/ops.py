@@ -1932,3 +1932,49 @@ def rerank_jaccard(idx: torch.Tensor, val: torch.Tensor, cnt: torch.Tensor, col_
                                        _ptr(inv_row), _ptr(inv_val), _ptr(rowmax), Q, G, oml, lam, _ptr(dist),
                                        int(dist.stride(0)), _ptr(ws), ws.numel(), _stream(dev)), "rerank_jaccard")
     return dist
+
+
+# ---------------------------------------------------------------------------------------------
+JITTER_OUT = {"uint8": 0, "float": 1}     # OIBL_JITTER_U8_NHWC, OIBL_JITTER_F32_NCHW
+JITTER_RECORD_WORDS = 8                   # a record: four op codes, three fp32 factors (their bits), the hue byte
+JITTER_MAX_PIXELS = 1 << 28
+
+
+def color_jitter(u8: torch.Tensor, params: Optional[torch.Tensor], out: str = "float", mean=REF_MEAN,
+                 std=REF_STD) -> torch.Tensor:
+    """Training colour jitter of a raw batch on the device (oibl_color_jitter_u8): u8 [N][H][W][3] uint8, `params`
+    int32 [N][8] — one record per image: the op codes in application order (0 brightness, 1 contrast, 2 saturation,
+    3 hue, -1 skip), the bits of the fp32 brightness / contrast / saturation factors, the hue shift byte
+    (openibl_amd.augment.ColorJitter.draw builds them) — or None for no jitter.
+    out='uint8': the jittered images [N][H][W][3], PIL's bits; out='float': [N][3][H][W] float32, the loader's
+    ToTensor + Normalize of those bytes ((u / 255 - mean) / std): what forward_train takes."""
+    if out not in JITTER_OUT:
+        raise ValueError(f"color_jitter: out must be 'float' or 'uint8', not {out!r}")
+    if u8.dtype != torch.uint8:
+        raise ValueError(f"color_jitter expects a uint8 batch, got {u8.dtype}")
+    if u8.dim() != 4 or u8.shape[3] != 3 or min(u8.shape) < 1:
+        raise ValueError(f"color_jitter expects [N][H][W][3], got {tuple(u8.shape)}")
+    N, H, W, _ = u8.shape
+    if H * W > JITTER_MAX_PIXELS or N > 65535:
+        raise ValueError(f"color_jitter: N <= 65535 and H * W <= 2^28, got {tuple(u8.shape)}")
+    if params is not None:
+        if params.dtype != torch.int32:
+            raise ValueError(f"color_jitter: params must be int32 records, got {params.dtype}")
+        if tuple(params.shape) != (N, JITTER_RECORD_WORDS):
+            raise ValueError(f"color_jitter: params must be [{N}][{JITTER_RECORD_WORDS}], got {tuple(params.shape)}")
+    if not u8.is_contiguous() or (params is not None and not params.is_contiguous()):
+        raise ValueError("openibl_amd: tensors must be contiguous")
+    dev = _need_cuda(u8, params)
+    lib = _lib.load()
+    if out == "uint8":
+        res = torch.empty((N, H, W, 3), dtype=torch.uint8, device=dev)
+    else:
+        res = torch.empty((N, 3, H, W), dtype=torch.float32, device=dev)
+    ws = None
+    if params is not None:
+        ws = workspace(lib.oibl_color_jitter_u8_workspace_bytes(N, H, W), dev, slot="color_jitter")
+    m3 = (C.c_float * 3)(*[float(v) for v in mean])
+    s3 = (C.c_float * 3)(*[float(v) for v in std])
+    _lib.check(lib.oibl_color_jitter_u8(_ptr(u8), N, H, W, _ptr(params), JITTER_OUT[out], m3, s3, _ptr(res),
+                                        _ptr(ws), 0 if ws is None else ws.numel(), _stream(dev)), "color_jitter_u8")
+    return res
