@@ -2130,6 +2130,34 @@ int oibl_debug_set_conv11_valu(int on) {
   g_conv11_valu = on ? 1 : 0;
   return OIBL_OK;
 }
+
+// One uint8 stem alone (tests/test_gpu_stem_u8.py): x [N][H][W][3] uint8 -> out [N][H/2][W/2][64] in the precision's
+// container, through the launch vgg_forward_impl makes for raw bytes — vgg_stem_kernel<true> (bf16),
+// vgg_stem_x3_kernel<false, true> (bf16x3), vgg_stem_x3_kernel<true, true> (f16mx; act_scale and the range flag are
+// its alone).  mean3 / std3 are host pointers.  The 4-byte stems fetch aligned dwords: x must start on one, the
+// condition under which vgg_forward_impl takes this route.
+int oibl_debug_vgg16_stem_u8(const void* x_u8_nhwc, int N, int H, int W, const float* mean3_host, const float* std3_host,
+                             const float* w1_oihw, const float* b1, const void* packed_w2, const float* b2,
+                             int precision, float act_scale, void* range_flag_dev_u32, void* out, void* stream) {
+  OIBL_REQUIRE(x_u8_nhwc && mean3_host && std3_host && w1_oihw && b1 && packed_w2 && b2 && out,
+               "debug_vgg16_stem_u8: null pointer");
+  OIBL_REQUIRE(precision == OIBL_BF16 || precision == OIBL_BF16X3 || precision == OIBL_F16MX,
+               "debug_vgg16_stem_u8: bad precision %d (bf16, bf16x3 or f16mx)", precision);
+  const bool mx = precision == OIBL_F16MX;
+  OIBL_REQUIRE(N > 0 && H >= 2 && W >= (mx ? 3 : 2), "debug_vgg16_stem_u8: bad shape N=%d H=%d W=%d (needs H >= 2, W >= %d)",
+               N, H, W, mx ? 3 : 2);
+  OIBL_REQUIRE(stem_eligible(N, H, W), "debug_vgg16_stem_u8: input of %d x 3 x %d x %d exceeds 3.5 GB", N, H, W);
+  OIBL_REQUIRE((uintptr_t)packed_w2 % 16 == 0 && (uintptr_t)out % 16 == 0,
+               "debug_vgg16_stem_u8: packed weights / output must be 16-byte aligned");
+  if (precision == OIBL_BF16)
+    return launch_vgg_stem(x_u8_nhwc, N, H, W, mean3_host, std3_host, w1_oihw, b1, packed_w2, b2, out, (hipStream_t)stream);
+  OIBL_REQUIRE((uintptr_t)x_u8_nhwc % 4 == 0,
+               "debug_vgg16_stem_u8: the bf16x3 / f16mx stems need a 4-byte aligned image (vgg_forward_impl normalises "
+               "a misaligned one in a pass of its own)");
+  OIBL_REQUIRE(mx || act_scale == 1.f, "debug_vgg16_stem_u8: act_scale %g belongs to f16mx only", (double)act_scale);
+  return launch_vgg_stem_x3(x_u8_nhwc, N, H, W, w1_oihw, b1, packed_w2, b2, out, (hipStream_t)stream, mx,
+                            mx ? (unsigned*)range_flag_dev_u32 : nullptr, mean3_host, std3_host, mx ? act_scale : 1.f);
+}
 #endif
 
 int oibl_conv1_1_nchw(const float* x_nchw, int N, int H, int W, const float* w_oihw,

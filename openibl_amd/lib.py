@@ -222,6 +222,8 @@ _HOOKS = {"oibl_debug_set_regstage": (c_int, [c_int]),
           "oibl_debug_set_stem_mx12": (c_int, [c_int]),
           "oibl_debug_set_stem_mx_flag": (c_int, [c_void_p]),
           "oibl_debug_last_stem_mx_route": (c_int, []),
+          "oibl_debug_vgg16_stem_u8": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                               c_void_p, c_void_p, c_int, C.c_float, c_void_p, c_void_p, c_void_p]),
           "oibl_debug_set_prof_buffer": (c_int, [c_void_p])}
 
 ABI_VERSION = 3

@@ -3,7 +3,8 @@ loader's bytes themselves (csrc/stem.hip, vgg_stem_x3_kernel<MX, U8>) — no nor
 bytes over PCIe.  Normalize is one fma per value there (within 2^-16 of the loader's three rounded operations:
 tests/test_stem_u8_cpu.py), so the result is not bit-identical to the fp32-input route; it is checked against it
 (a few 1e-6), against the oracle on the loader's own tensor (1e-4), on border-heavy odd sizes, and the old route
-(normalising pass, test hook) stays bit-identical to the fp32 input."""
+(normalising pass, test hook) stays bit-identical to the fp32 input.
+The stems alone — emulation, alignments, batch mates, guard bytes — are in tests/test_gpu_stem_u8.py."""
 import pytest
 import torch
 

@@ -23,15 +23,22 @@ def _split(v):
     return hi.numpy(), lo.numpy()
 
 
-def test_fma_normalisation_is_within_an_ulp_of_the_loaders_arithmetic():
+def fma_mirror(c):
+    """(loader's value, the fma's value) of channel c for the 256 bytes, float32 (also held against
+    tests/helpers/stem_u8_ref.fma_normalise in tests/test_stem_u8_ref_cpu.py)."""
     u = np.arange(256, dtype=np.float32)
+    m, s = np.float32(MEAN[c]), np.float32(STD[c])
+    ref = ((u / np.float32(255.0)) - m) / s                          # three rounded fp32 operations
+    a = np.float32(1.0 / (255.0 * float(s)))
+    b = np.float32(-float(m) / float(s))
+    fast = (u.astype(np.float64) * float(a) + float(b)).astype(np.float32)   # one fma: exact product, one rounding
+    return ref, fast
+
+
+def test_fma_normalisation_is_within_an_ulp_of_the_loaders_arithmetic():
     worst, lo_diff = 0.0, 0
     for c in range(3):
-        m, s = np.float32(MEAN[c]), np.float32(STD[c])
-        ref = ((u / np.float32(255.0)) - m) / s                          # three rounded fp32 operations
-        a = np.float32(1.0 / (255.0 * float(s)))
-        b = np.float32(-float(m) / float(s))
-        fast = (u.astype(np.float64) * float(a) + float(b)).astype(np.float32)   # one fma: exact product, one rounding
+        ref, fast = fma_mirror(c)
         worst = max(worst, float(np.abs(ref.astype(np.float64) - fast.astype(np.float64)).max()))
         # the loader rounds u / 255 - mean at magnitude <= 1 (ulp 6e-8) and then divides by 1 / 255: ITS result
         # carries up to 255 x 6e-8 = 1.5e-5 of rounding; the fma's single rounding is the more exact of the two
