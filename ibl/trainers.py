@@ -59,14 +59,15 @@ def _stack_tuples(inputs):
 
 def _augment_tuples(augment, imgs, gpu):
     """imgs [B][N][H][W][3] uint8 on the host (the loader's raw tuples, `get_transformer_train(..., as_uint8=True)`)
-    -> [B][N][3][H][W] float32 on the device: the bytes cross as they are, and `augment` (an
-    openibl_amd.augment.ColorJitter: [n][H][W][3] uint8 -> [n][3][H][W] float32) jitters every image on its own."""
+    -> [B][N][3][H'][W'] float32 on the device: the bytes cross as they are, and `augment` (an
+    openibl_amd.augment.ColorJitter: [n][H][W][3] uint8 -> [n][3][H][W] float32; or a Compose of it with an
+    openibl_amd.augment.Resize behind it, which hands back the target size H' x W') jitters every image on its own."""
     if imgs.dtype != torch.uint8 or imgs.dim() != 5 or imgs.shape[-1] != 3:
         raise ValueError(f"a trainer with `augment` set takes uint8 tuples [B][N][H][W][3] from the loader "
                          f"(get_transformer_train(..., as_uint8=True)), got {imgs.dtype} {tuple(imgs.shape)}")
     B, N, H, W, _ = imgs.shape
     out = augment(imgs.contiguous().cuda(gpu).view(B * N, H, W, 3))
-    return out.view(B, N, 3, H, W)
+    return out.view(B, N, 3, out.shape[-2], out.shape[-1])
 
 
 class Trainer(object):

@@ -724,6 +724,41 @@ int oibl_color_jitter_u8(const uint8_t* x_nhwc, int N, int H, int W, const void*
                          const float* mean3_host, const float* std3_host, void* out, void* ws, size_t ws_bytes,
                          void* stream);
 
+/* ---- bilinear resize of raw uint8 batches -------------------------------------------------- *
+ * Replaces Resize of get_transformer_train / get_transformer_test (ibl/utils/data/__init__.py:
+ * img.resize((w, h), Image.BILINEAR) through torchvision and PIL on the host) and, for out_kind
+ * OIBL_JITTER_F32_NCHW, the ToTensor + Normalize behind it.  The arithmetic is PIL's 8-bit resampling
+ * (csrc/resize_tables.h, csrc/resize.hip state it): per axis a table of windows and 22-bit fixed-point triangle
+ * weights computed in IEEE double, then two integer passes, horizontal first, with a uint8 intermediate.  The uint8
+ * result equals PIL's bit for bit; a pass whose size does not change is the exact identity.
+ *   x_nhwc [N][H][W][3] uint8   the stored images (any byte alignment).
+ *   H2, W2                      the target size.  One path only: a workgroup keeps the source rows of its tile of
+ *                               16 x 64 output pixels in LDS (at most 64 KiB of it), so H <= 16 H2 and W <= 16 W2
+ *                               (a downscale factor of at most 16 per axis; upscaling is not limited); beyond
+ *                               that OIBL_E_INVALID with a message that names the limit.  N <= 65535, every size
+ *                               <= 32768.
+ *   out_kind OIBL_JITTER_U8_NHWC   out [N][H2][W2][3] uint8 (any byte alignment); mean3_host / std3_host unused.
+ *            OIBL_JITTER_F32_NCHW  out [N][3][H2][W2] fp32 = (float(u8) / 255.0f - mean_c) / std_c, both divisions
+ *                               IEEE: what oibl_color_jitter_u8 without records gives on the resized bytes.
+ * Three launches: the two tables are built ON THE DEVICE into the workspace (fp64, one thread per output
+ * coordinate), then one fused launch runs both passes.  No host memory, no copy and nothing owned by the library:
+ * the call is stream-ordered and can be captured into a graph.  Integer sums, no atomics: identical bits from run
+ * to run, and an image's result does not depend on the rest of the batch.
+ * Workspace: per axis int32 bounds[out][2] and int32 coeff[out][ksize], each rounded up to 256 bytes (it does not
+ * depend on N); oibl_resize_u8_workspace_bytes returns 0 for a shape oibl_resize_u8 rejects.
+ *
+ * oibl_resize_u8_tables builds the tables of ONE axis, in_size -> out_size samples, into caller memory (device,
+ * 4-byte aligned): bounds[out_size][2] = {first source sample, number of taps} and coeff[out_size][ksize], the taps'
+ * weights times 2^22, rounded, zero behind the last tap; ksize = 2 ceil(max(in_size / out_size, 1)) + 1 is the row
+ * length and is written to *ksize_out_host_or_null on the host before the launch.  ksize_capacity: the row length
+ * the caller sized coeff for; a larger ksize is OIBL_E_INVALID and nothing is launched.  No scale limit here. */
+size_t oibl_resize_u8_workspace_bytes(int N, int H, int W, int H2, int W2);
+int oibl_resize_u8_tables(int in_size, int out_size, int32_t* bounds, int32_t* coeff, int ksize_capacity,
+                          int* ksize_out_host_or_null, void* stream);
+int oibl_resize_u8(const uint8_t* x_nhwc, int N, int H, int W, int H2, int W2, int out_kind,
+                   const float* mean3_host, const float* std3_host, void* out, void* ws, size_t ws_bytes,
+                   void* stream);
+
 /* ---- recall counting ---------------------------------------------------------------- *
  * Replaces the per-query Python loop of evaluate_all and spatial_nms
  * (ibl/evaluators.py:132-140, 149-160).  For every query, the rank (0-based, inside the

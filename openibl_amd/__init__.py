@@ -9,7 +9,8 @@ Layout
   pca.py           mirror of ibl.pca.PCA (load / infer)
   evaluators.py    mirror of ibl.evaluators (extract_*, pairwise_distance, evaluate_all, Evaluator)
   sharded.py       gallery-sharded top-k matching over torch.distributed (RCCL)
-  augment.py       training colour jitter for raw uint8 batches on the device (ColorJitter)
+  augment.py       training colour jitter and PIL's bilinear resize for raw uint8 batches on the device
+                   (ColorJitter, Resize, Compose)
   trunk_cache.py   stored pool4 maps of the training images: re-extraction with the trunk frozen (TrunkCache)
 
 The `ibl` package at the repository root re-exports these under the reference's module names so

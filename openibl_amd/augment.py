@@ -1,13 +1,17 @@
-"""Training augmentation on the device: `ColorJitter` for raw uint8 batches.
+"""Training augmentation on the device: `ColorJitter`, `Resize` and `Compose` for raw uint8 batches.
 
 The reference's training transform is ColorJitter(0.7, 0.7, 0.7, 0.5) -> Resize -> ToTensor -> Normalize
 (ibl/utils/data/__init__.py:29-35 of the reference, through torchvision and PIL on the host).  Here the loader hands
-over the resized raw bytes (`get_transformer_train(..., as_uint8=True)`), the batch crosses to the device as uint8 and
-one call of ops.color_jitter applies the jitter with PIL's arithmetic — bit for bit — and the normalisation behind it.
+over raw bytes, the batch crosses to the device as uint8, ops.color_jitter applies the jitter and ops.resize_u8 the
+resize — both with PIL's arithmetic, bit for bit — and the normalisation rides behind the last of them:
 
-Limit: the reference jitters BEFORE Resize, this flow after it.  The two agree bit for bit exactly when the stored
-images already have the target size (Pitts: 640 x 480); otherwise both are valid augmentations of the same
-distribution that differ in rounding."""
+    get_transformer_train(480, 640, as_uint8=True, resize=False)           # the decoded bytes at their stored size
+    augment = Compose(ColorJitter(0.7, 0.7, 0.7, 0.5, out='uint8'), Resize(480, 640))      # the reference's order
+
+Limit, only when the HOST resizes (`get_transformer_train(..., as_uint8=True)` with its default resize=True and a
+bare ColorJitter as `augment`): the reference jitters BEFORE Resize, that flow after it.  The two agree bit for bit
+exactly when the stored images already have the target size (Pitts: 640 x 480); otherwise both are valid augmentations
+of the same distribution that differ in rounding.  With the device resize the order is the reference's."""
 from __future__ import annotations
 
 import numbers
@@ -112,3 +116,74 @@ class ColorJitter(object):
     def __repr__(self):
         return (f"{self.__class__.__name__}(brightness={self.brightness}, contrast={self.contrast}, "
                 f"saturation={self.saturation}, hue={self.hue})")
+
+
+def aspect_size(height: int, width: int, h: int, w: int):
+    """The target (height, width) of the reference's test transform for Tokyo queries (`keep_aspect`): the shorter
+    side of an h x w image becomes max(height, width), the other one int(s * long / short) — the arithmetic of
+    ibl.utils.data._TestTransform, in the same types."""
+    s = max(height, width)
+    if w <= h:
+        return int(s * h / w), s
+    return s, int(s * w / h)
+
+
+class Resize(object):
+    """The reference's Resize for a raw uint8 batch on the device: `img.resize((width, height), Image.BILINEAR)` of
+    every image, PIL's bits (ops.resize_u8).  keep_aspect=True: the target of every batch is computed from its own
+    size as the test transform does for Tokyo queries (`aspect_size`).  `out`: 'float' (normalised [N][3][H'][W']
+    float32, what forward_train takes) or 'uint8' ([N][H'][W'][3], what the uint8 stems and a further stage take)."""
+
+    def __init__(self, height: int, width: int, keep_aspect: bool = False, out: str = "float"):
+        if isinstance(height, bool) or isinstance(width, bool) or \
+                not isinstance(height, numbers.Integral) or not isinstance(width, numbers.Integral):
+            raise TypeError(f"Resize: height and width must be integers, got {height!r}, {width!r}")
+        if height < 1 or width < 1:
+            raise ValueError(f"Resize: the target size must be positive, got {height} x {width}")
+        if out not in ops.JITTER_OUT:
+            raise ValueError(f"Resize: out must be 'float' or 'uint8', not {out!r}")
+        self.height, self.width = int(height), int(width)
+        self.keep_aspect = bool(keep_aspect)
+        self.out = out
+
+    def target(self, h: int, w: int):
+        """(height, width) of the result for a source of h x w."""
+        if self.keep_aspect:
+            return aspect_size(self.height, self.width, int(h), int(w))
+        return self.height, self.width
+
+    def __call__(self, u8_batch: torch.Tensor) -> torch.Tensor:
+        if u8_batch.dim() != 4:
+            raise ValueError(f"Resize expects [N][H][W][3], got {tuple(u8_batch.shape)}")
+        return ops.resize_u8(u8_batch, self.target(u8_batch.shape[1], u8_batch.shape[2]), out=self.out)
+
+    def __repr__(self):
+        return (f"{self.__class__.__name__}(height={self.height}, width={self.width}, "
+                f"keep_aspect={self.keep_aspect}, out={self.out!r})")
+
+
+class Compose(object):
+    """Chains stages on a device batch: Compose(a, b)(x) = b(a(x)).  Every stage but the last must hand uint8 on
+    (out='uint8').  The reference's training transform is
+    Compose(ColorJitter(0.7, 0.7, 0.7, 0.5, out='uint8'), Resize(480, 640)).
+    Keyword arguments of a call go to the FIRST stage (the `records=` of a ColorJitter replay)."""
+
+    def __init__(self, *stages):
+        if not stages:
+            raise ValueError("Compose needs at least one stage")
+        for k, stage in enumerate(stages):
+            if not callable(stage):
+                raise TypeError(f"Compose: stage {k} is not callable: {stage!r}")
+            if k + 1 < len(stages) and getattr(stage, "out", "uint8") != "uint8":
+                raise ValueError(f"Compose: stage {k} ({stage!r}) hands float on; every stage but the last needs "
+                                 f"out='uint8'")
+        self.stages = tuple(stages)
+
+    def __call__(self, batch: torch.Tensor, **first_stage_args) -> torch.Tensor:
+        batch = self.stages[0](batch, **first_stage_args)
+        for stage in self.stages[1:]:
+            batch = stage(batch)
+        return batch
+
+    def __repr__(self):
+        return f"{self.__class__.__name__}({', '.join(repr(s) for s in self.stages)})"

@@ -163,7 +163,7 @@ __global__ __launch_bounds__(CJ_THREADS) void jitter_apply_kernel(const uint8_t*
       for (int ch = 0; ch < 3; ++ch) {
         float v[CJ_GROUP];
 #pragma unroll
-        for (int j = 0; j < CJ_GROUP; ++j) v[j] = ((float)c[3 * j + ch] / 255.0f - mu[ch]) / sd[ch];
+        for (int j = 0; j < CJ_GROUP; ++j) v[j] = cj_normalize(c[3 * j + ch], mu[ch], sd[ch]);
         float* plane = outf + (size_t)ch * geo.HW + px;
         if (out_wide && full) {
           *reinterpret_cast<f32x4_t*>(plane) = f32x4_t{v[0], v[1], v[2], v[3]};

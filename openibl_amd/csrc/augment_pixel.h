@@ -32,6 +32,9 @@ OIBL_PX int cj_luma(int r, int g, int b) { return (19595 * r + 38470 * g + 7471 
 
 OIBL_PX int cj_clip8(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
 
+// ToTensor + Normalize of one byte, both divisions IEEE: the fp32 output of augment.hip and of resize.hip
+OIBL_PX float cj_normalize(int c, float mean, float std) { return ((float)c / 255.0f - mean) / std; }
+
 // Image.blend(degenerate d, image x, a) of one byte; `inside` = 0 <= a <= 1, where PIL does not clip
 OIBL_PX int cj_blend(int d, int x, float a, bool inside) {
   const float df = (float)d;

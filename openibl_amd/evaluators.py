@@ -77,9 +77,10 @@ FAST_EXTRACTION = True   # False: batch-by-batch eager launches (the cross-check
 
 
 def _extract_local(model, data_loader, vlad, pca, gpu, print_freq, rank, scales=None, store_dtype=None,
-                   use_graphs=True):
+                   use_graphs=True, input_resize=None):
     """Run the loader of this rank; returns the [n_local][d] descriptor matrix ON DEVICE, in
     `store_dtype` (None = float32; float16 / bfloat16 = 16-bit descriptor storage).
+    `input_resize`: as in `extract_features`.
 
     Embed* models take the replayed route of openibl_amd.extract (hipGraph per batch shape, batches
     alternating between two lanes, H2D on a copy stream, descriptors written straight into a
@@ -92,13 +93,16 @@ def _extract_local(model, data_loader, vlad, pca, gpu, print_freq, rank, scales=
     if FAST_EXTRACTION and scales is None and extract.fast_path_supported(model):
         return extract.extract_descriptors(model, data_loader, vlad=vlad, pca=pca, gpu=gpu,
                                            print_freq=print_freq, rank=rank, store_dtype=store_dtype,
-                                           use_graphs=use_graphs)
+                                           use_graphs=use_graphs, input_resize=input_resize)
+    resize = extract.input_resizer(input_resize)
     batch_t, data_t = _Meter(), _Meter()
     chunks = []
     end = time.time()
     with torch.no_grad():
         for i, batch in enumerate(data_loader):
             imgs = batch[0]
+            if resize is not None:
+                imgs = extract.apply_input_resize(resize, torch.as_tensor(imgs), _device(gpu))
             data_t.update(time.time() - end)
             out = extract_cnn_feature(model, imgs, vlad, gpu=gpu, scales=scales)
             if pca is not None:
@@ -141,10 +145,17 @@ def _gather_all(local: torch.Tensor, sync_gather: bool, rank: int, world: int) -
 
 
 def extract_features(model, data_loader, dataset, print_freq=10, vlad=True, pca=None, gpu=None,
-                     sync_gather=False, scales=None, store_dtype=None, use_graphs=True, trunk_cache=None):
+                     sync_gather=False, scales=None, store_dtype=None, use_graphs=True, trunk_cache=None,
+                     input_resize=None):
     """OrderedDict fname -> CPU descriptor for every item of `dataset` (evaluators.py:36-103).
     `use_graphs=False`: the two-lane route without hipGraph capture (loaders whose batch shapes rarely
     repeat; `openibl_amd.extract.MAX_CACHED_SHAPES` bounds the captured shapes kept otherwise).
+
+    input_resize (extension): (height, width), or an `openibl_amd.augment.Resize(..., out='uint8')` (keep_aspect for
+    Tokyo queries).  The loader then delivers raw uint8 [N][H][W][3] batches at their STORED size
+    (`get_transformer_test(..., as_uint8=True, resize=False)`) and every batch is resized on the device right after
+    it got there — the reference's Resize, PIL's bits — before it enters the usual flow.  A float32 batch raises
+    ValueError.
 
     Each rank extracts the slice its DistributedSliceSampler yields; slices are gathered
     rank-major and truncated to len(dataset) (the wrap-around padding of the last slices).
@@ -160,7 +171,8 @@ def extract_features(model, data_loader, dataset, print_freq=10, vlad=True, pca=
         trunk_cache.check(model, len(dataset))
         local = trunk_cache.descriptors(model, vlad, store_dtype, pca)
     else:
-        local = _extract_local(model, data_loader, vlad, pca, gpu, print_freq, rank, scales, store_dtype, use_graphs)
+        local = _extract_local(model, data_loader, vlad, pca, gpu, print_freq, rank, scales, store_dtype, use_graphs,
+                               input_resize)
     allf = _gather_all(local, sync_gather, rank, world)[: len(dataset)]
     features = OrderedDict()
     for item, row in zip(dataset, allf):

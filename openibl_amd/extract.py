@@ -558,14 +558,45 @@ def _module_caches(core, pca=None):
     return collect
 
 
+def input_resizer(input_resize):
+    """The `input_resize` argument of the extraction entry points -> None or a callable on device uint8 batches that
+    hands uint8 back: (height, width) becomes an openibl_amd.augment.Resize(height, width, out='uint8'); a Resize
+    (keep_aspect for Tokyo queries) is taken as it is and must have out='uint8'."""
+    if input_resize is None:
+        return None
+    from .augment import Resize
+    if isinstance(input_resize, Resize):
+        if input_resize.out != "uint8":
+            raise ValueError("input_resize: the Resize must hand uint8 on (out='uint8'): the model's uint8 stem "
+                             "normalises the resized bytes")
+        return input_resize
+    if isinstance(input_resize, (tuple, list)) and len(input_resize) == 2:
+        return Resize(int(input_resize[0]), int(input_resize[1]), out="uint8")
+    raise TypeError(f"input_resize must be None, (height, width) or an openibl_amd.augment.Resize, "
+                    f"not {input_resize!r}")
+
+
+def apply_input_resize(resize, imgs: torch.Tensor, dev) -> torch.Tensor:
+    """A loader's raw uint8 batch [N][H][W][3] (host or device) -> the resized uint8 batch on the device, computed on
+    the current stream.  The result is a temporary of that stream: GraphedForward and EagerLanes make their lane wait
+    for the caller's stream and `record_stream` a device-resident source, so it may be dropped after the call."""
+    if imgs.dtype != torch.uint8:
+        raise ValueError(f"input_resize resizes raw uint8 [N][H][W][3] batches (a loader with as_uint8=True, "
+                         f"resize=False), got {imgs.dtype} {tuple(imgs.shape)}")
+    return resize(imgs.contiguous().to(dev, non_blocking=True))
+
+
 def extract_descriptors(model, data_loader, vlad=True, pca=None, gpu=None, print_freq=10, rank=0,
-                        store_dtype=None, use_graphs: bool = True) -> torch.Tensor:
+                        store_dtype=None, use_graphs: bool = True, input_resize=None) -> torch.Tensor:
     """Descriptors of every item one rank's loader yields, in loader order, as one device matrix
     [n_local][d] (float32, or `store_dtype`).  The caller has put the model in eval mode and loaded
     `pca`.  Batches may be float32 [N][3][H][W] (normalised) or uint8 [N][H][W][3] (raw), pinned or
-    not, of any mix of shapes."""
+    not, of any mix of shapes.  `input_resize` (`input_resizer`): every batch must be uint8 and is resized on the
+    device right after it got there, with PIL's bits; the loop below then sees a device-resident uint8 batch of the
+    target size — shape keys, capture, lanes and staging know nothing of the stored size."""
     core = unwrap_model(model)
     dev = torch.device("cuda", torch.cuda.current_device() if gpu is None else gpu)
+    resize = input_resizer(input_resize)
     backbone = core.base_model.features_nhwc
     head = _head_fn(core, vlad, pca, store_dtype)
     try:
@@ -589,6 +620,8 @@ def extract_descriptors(model, data_loader, vlad=True, pca=None, gpu=None, print
             imgs = batch[0]
             if not torch.is_tensor(imgs):
                 imgs = torch.as_tensor(imgs)
+            if resize is not None:
+                imgs = apply_input_resize(resize, imgs, dev)
             if imgs.dtype != torch.uint8 and imgs.dtype != torch.float32:
                 imgs = imgs.float()
             imgs = imgs.contiguous()

@@ -1978,3 +1978,74 @@ def color_jitter(u8: torch.Tensor, params: Optional[torch.Tensor], out: str = "f
     _lib.check(lib.oibl_color_jitter_u8(_ptr(u8), N, H, W, _ptr(params), JITTER_OUT[out], m3, s3, _ptr(res),
                                         _ptr(ws), 0 if ws is None else ws.numel(), _stream(dev)), "color_jitter_u8")
     return res
+
+
+# ---------------------------------------------------------------------------------------------
+RESIZE_MAX_SCALE = 16         # RS_MAX_SCALE of csrc/resize_tables.h: the largest in / out per axis
+RESIZE_MAX_DIM = 32768
+
+
+def _resize_ksize(in_size: int, out_size: int) -> int:
+    """Entries per row of an axis's coefficient table: 2 ceil(max(in / out, 1)) + 1 (PIL's ksize, bilinear)."""
+    import math
+    return int(math.ceil(max(in_size / out_size, 1.0))) * 2 + 1
+
+
+def resize_u8_tables(in_size: int, out_size: int, device=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The tables of one axis of the device resize (oibl_resize_u8_tables), built by the kernel: int32
+    bounds [out_size][2] = {first source sample, taps} and int32 coeff [out_size][ksize], the weights times 2^22."""
+    in_size, out_size = int(in_size), int(out_size)
+    if not (1 <= in_size <= RESIZE_MAX_DIM and 1 <= out_size <= RESIZE_MAX_DIM):
+        raise ValueError(f"resize_u8_tables: sizes must be in [1, {RESIZE_MAX_DIM}], got {in_size} -> {out_size}")
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    lib = _lib.load()
+    ksize = _resize_ksize(in_size, out_size)
+    bounds = torch.empty((out_size, 2), dtype=torch.int32, device=dev)
+    coeff = torch.empty((out_size, ksize), dtype=torch.int32, device=dev)
+    got = C.c_int(0)
+    with torch.cuda.device(dev):
+        _lib.check(lib.oibl_resize_u8_tables(in_size, out_size, _ptr(bounds), _ptr(coeff), ksize, C.byref(got),
+                                             _stream(dev)), "resize_u8_tables")
+    assert got.value == ksize
+    return bounds, coeff
+
+
+def resize_u8(u8: torch.Tensor, size, out: str = "uint8", mean=REF_MEAN, std=REF_STD) -> torch.Tensor:
+    """Bilinear resize of a raw batch on the device (oibl_resize_u8), PIL's bits: u8 [N][H][W][3] uint8,
+    size = (height, width) of the result.  It is `Image.resize((width, height), Image.BILINEAR)` of every image —
+    what the reference's Resize does on the host — bit for bit.  out='uint8': [N][height][width][3];
+    out='float': [N][3][height][width] float32, the loader's ToTensor + Normalize of those bytes
+    ((u / 255 - mean) / std).  An axis may shrink by a factor of at most RESIZE_MAX_SCALE (the source rows of a
+    tile are kept in LDS); upscaling is not limited."""
+    if out not in JITTER_OUT:
+        raise ValueError(f"resize_u8: out must be 'float' or 'uint8', not {out!r}")
+    if u8.dtype != torch.uint8:
+        raise ValueError(f"resize_u8 expects a uint8 batch, got {u8.dtype}")
+    if u8.dim() != 4 or u8.shape[3] != 3 or min(u8.shape) < 1:
+        raise ValueError(f"resize_u8 expects [N][H][W][3], got {tuple(u8.shape)}")
+    if not isinstance(size, (tuple, list)) or len(size) != 2:
+        raise ValueError(f"resize_u8: size must be (height, width), got {size!r}")
+    H2, W2 = int(size[0]), int(size[1])
+    N, H, W, _ = u8.shape
+    if H2 < 1 or W2 < 1:
+        raise ValueError(f"resize_u8: the target size must be positive, got {H2} x {W2}")
+    if max(H, W, H2, W2) > RESIZE_MAX_DIM or N > 65535:
+        raise ValueError(f"resize_u8: N <= 65535 and every size <= {RESIZE_MAX_DIM}, got {tuple(u8.shape)} -> "
+                         f"{H2} x {W2}")
+    if H > RESIZE_MAX_SCALE * H2 or W > RESIZE_MAX_SCALE * W2:
+        raise ValueError(f"resize_u8: {H} x {W} -> {H2} x {W2} shrinks an axis by more than the limit of "
+                         f"{RESIZE_MAX_SCALE}")
+    if not u8.is_contiguous():
+        raise ValueError("openibl_amd: tensors must be contiguous")
+    dev = _need_cuda(u8)
+    lib = _lib.load()
+    if out == "uint8":
+        res = torch.empty((N, H2, W2, 3), dtype=torch.uint8, device=dev)
+    else:
+        res = torch.empty((N, 3, H2, W2), dtype=torch.float32, device=dev)
+    ws = workspace(lib.oibl_resize_u8_workspace_bytes(N, H, W, H2, W2), dev, slot="resize_u8")
+    m3 = (C.c_float * 3)(*[float(v) for v in mean])
+    s3 = (C.c_float * 3)(*[float(v) for v in std])
+    _lib.check(lib.oibl_resize_u8(_ptr(u8), N, H, W, H2, W2, JITTER_OUT[out], m3, s3, _ptr(res), _ptr(ws),
+                                  ws.numel(), _stream(dev)), "resize_u8")
+    return res

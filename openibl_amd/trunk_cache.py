@@ -84,11 +84,15 @@ class TrunkCache:
 
     # ---- fill -----------------------------------------------------------------------------------
     @classmethod
-    def fill(cls, model, loader, dataset, gpu=None, max_bytes: Optional[int] = None) -> "TrunkCache":
+    def fill(cls, model, loader, dataset, gpu=None, max_bytes: Optional[int] = None,
+             input_resize=None) -> "TrunkCache":
         """Run `loader` (the extraction loader over `dataset`, fp32 [N][3][H][W] or uint8 [N][H][W][3] batches in
         dataset order) once, eagerly, under no_grad in eval mode, and keep every batch's stored pool4 activation.
-        max_bytes: refuse (ValueError) a cache above it; default a quarter of the device's free memory now."""
+        max_bytes: refuse (ValueError) a cache above it; default a quarter of the device's free memory now.
+        input_resize: as in `extract_features` — the loader's raw uint8 batches are resized on the device first."""
         from .evaluators import _rank_world
+        from .extract import apply_input_resize, input_resizer
+        resize = input_resizer(input_resize)
         rank, world = _rank_world()
         if world != 1:
             raise RuntimeError(
@@ -116,6 +120,8 @@ class TrunkCache:
                 imgs = batch[0]
                 if not torch.is_tensor(imgs):
                     imgs = torch.as_tensor(imgs)
+                if resize is not None:
+                    imgs = apply_input_resize(resize, imgs, dev)
                 if imgs.dtype != torch.uint8 and imgs.dtype != torch.float32:
                     imgs = imgs.float()
                 if imgs.dim() != 4:
