@@ -366,6 +366,28 @@ int oibl_netvlad_backward(const void* feat, int N, int P, int K, int C, int prec
                           const float* grad_vlad_norm, float* grad_assign_w, float* grad_centroids,
                           float* grad_feat, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- NetVLAD + intra-norm + L2 for other cluster counts: forward and gradients ------- *
+ * The same two functions as oibl_netvlad_forward (fp32 map) and oibl_netvlad_backward for K = 16, 32, ..., 128
+ * clusters (any multiple of 16; K = 64 is accepted too and agrees with the entry points above to rounding, not bit
+ * for bit), C = 512, feat [N][P][C] fp32, any N >= 1 and P >= 1 with N ceil(P / 32) < 2^31.  Arguments, outputs and
+ * guarantees are those of the two entry points above without `precision`: exact fp32 on v_mfma_f32_32x32x2_f32, the
+ * backward stateless with fp64 logits, norms and normalisation gradients, every output optional and OVERWRITTEN, no
+ * floating-point atomics, bit-identical from run to run, and an image's vlad rows and grad_feat rows do not depend on
+ * its batch mates at ANY N (the pixels are cut into chunks of 32 whatever N is).
+ * Workspaces from the two queries (0 for an invalid shape; non-decreasing in N, P and K), 256-byte aligned; the other
+ * pointers 16-byte aligned.  Another K or C, a null input, no output, N or P < 1 return OIBL_E_INVALID with a message
+ * that names num_clusters / dim and the value, a short or misaligned workspace OIBL_E_WORKSPACE; nothing is launched
+ * then.                                                                                                            */
+size_t oibl_netvlad_k_workspace_bytes(int N, int P, int K, int C);
+int oibl_netvlad_forward_k(const void* feat, int N, int P, int K, int C, const float* assign_w,
+                           const float* centroids, int normalize_input, float* vlad_raw, float* vlad_norm,
+                           void* ws, size_t ws_bytes, void* stream);
+size_t oibl_netvlad_k_backward_workspace_bytes(int N, int P, int K, int C, int want_grad_feat);
+int oibl_netvlad_backward_k(const void* feat, int N, int P, int K, int C, const float* assign_w,
+                            const float* centroids, int normalize_input, const float* grad_vlad_norm,
+                            float* grad_assign_w, float* grad_centroids, float* grad_feat, void* ws,
+                            size_t ws_bytes, void* stream);
+
 /* ---- SFRS region head: gradients ---------------------------------------------------- *
  * The backward of oibl_region_vlad_forward and oibl_region_scores, i.e. of EmbedRegionNet._compute_region_sim
  * (ibl/models/netvlad.py:123-186) as torch autograd differentiates it under SFRSTrainer._forward

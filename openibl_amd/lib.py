@@ -73,6 +73,12 @@ SIGNATURES = {
     "oibl_netvlad_backward_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "oibl_netvlad_backward": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int,
                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "oibl_netvlad_k_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "oibl_netvlad_forward_k": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p,
+                                       c_void_p, c_void_p, c_size_t, c_void_p]),
+    "oibl_netvlad_k_backward_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "oibl_netvlad_backward_k": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p,
+                                        c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "oibl_conv3x3_backward_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
     "oibl_conv3x3_backward": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p,
                                       c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),

@@ -555,6 +555,10 @@ class EmbedRegionNet(_PrecisionMixin, nn.Module):
         return ops.global_maxpool_nhwc(feat), vlad
 
     def _tuple_shape(self, batch: int):
+        if int(self.net_vlad.num_clusters) != 64:
+            raise ValueError(f"EmbedRegionNet: the region head's kernels are built for num_clusters = 64 (got "
+                             f"{int(self.net_vlad.num_clusters)}); other cluster counts run in EmbedNet / EmbedNetPCA "
+                             f"and in this model's eval forward, not in its region similarities")
         T = int(self.tuple_size)
         if T <= 0 or batch % T:
             raise ValueError(f"EmbedRegionNet: a batch of {batch} images is not a multiple of tuple_size {T}")

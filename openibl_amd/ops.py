@@ -662,9 +662,24 @@ def _head_backward(ctx, head_backward, grad_out):
     return gx, gw, gc, None
 
 
+# The cluster counts the descriptor head runs for: K = 64 on the tuned kernels (oibl_netvlad_forward / _backward), every
+# other multiple of 16 up to 128 on the K-general ones (oibl_netvlad_forward_k / _backward_k, csrc/netvlad_k.hip).
+NETVLAD_CLUSTERS = tuple(range(16, 129, 16))
+
+
+def _head_clusters(what: str, K: int) -> bool:
+    """True where K takes the K-general entry points, False for the tuned K = 64 ones; another K raises before
+    any library call."""
+    if K not in NETVLAD_CLUSTERS:
+        raise ValueError(f"{what}: num_clusters must be one of {', '.join(map(str, NETVLAD_CLUSTERS))} (got {K})")
+    return K != 64
+
+
 def netvlad(feat: torch.Tensor, assign_w: torch.Tensor, centroids: torch.Tensor,
             normalize_input: bool = True, want_raw: bool = False, want_norm: bool = True):
-    """feat [N][h][w][C] (or [N][P][C]) T -> (vlad_raw [N][K][C] | None, vlad_norm [N][K*C] | None)."""
+    """feat [N][h][w][C] (or [N][P][C]) T -> (vlad_raw [N][K][C] | None, vlad_norm [N][K*C] | None).
+    K = 64: the tuned kernels, in the map's own element type.  K = 16, 32, 48, 80, 96, 112, 128: the K-general
+    fp32 kernels (oibl_netvlad_forward_k); a bf16 map is widened to fp32 first, as `netvlad_head` does."""
     dev = _need_cuda(feat, assign_w, centroids)
     p = BF16 if feat.dtype == torch.bfloat16 else F32
     if feat.dtype not in (torch.bfloat16, torch.float32):
@@ -672,7 +687,18 @@ def netvlad(feat: torch.Tensor, assign_w: torch.Tensor, centroids: torch.Tensor,
     N, C_ = int(feat.shape[0]), int(feat.shape[-1])
     P = feat.numel() // (N * C_)
     K, aw = _head_weights("netvlad", assign_w, centroids, C_)
+    general = _head_clusters("netvlad", K)
     lib = _lib.load()
+    if general:
+        if feat.dtype == torch.bfloat16:
+            feat = feat.float()
+        ws = workspace(lib.oibl_netvlad_k_workspace_bytes(N, P, K, C_), dev, "netvlad_k")
+        raw = torch.empty((N, K, C_), dtype=torch.float32, device=dev) if want_raw else None
+        nrm = torch.empty((N, K * C_), dtype=torch.float32, device=dev) if want_norm else None
+        _lib.check(lib.oibl_netvlad_forward_k(_ptr(feat), N, P, K, C_, _ptr(aw), _ptr(centroids),
+                                              int(normalize_input), _ptr(raw), _ptr(nrm), _ptr(ws), ws.numel(),
+                                              _stream(dev)), "netvlad_forward_k")
+        return raw, nrm
     ws_bytes = lib.oibl_netvlad_workspace_bytes(N, P, K, C_)
     ws = workspace(ws_bytes, dev, "netvlad")
     raw = torch.empty((N, K, C_), dtype=torch.float32, device=dev) if want_raw else None
@@ -689,7 +715,8 @@ def netvlad_backward(feat: torch.Tensor, assign_w: torch.Tensor, centroids: torc
     ibl/models/netvlad.py:44-61, 78-80; oibl_netvlad_backward).  feat [N][h][w][C] (or [N][P][C]) fp32, grad_out
     [N][K*C] fp32 = dL/d vlad_norm -> (grad_assign_w [K][C] | None, grad_centroids [K][C] | None, grad_feat like
     feat | None) for the letters in `want` ("w", "c", "x").  Stateless: the forward's intermediates are recomputed
-    from feat.  Bit-identical from run to run; an output does not depend on which others are asked for."""
+    from feat.  Bit-identical from run to run; an output does not depend on which others are asked for.  K = 64 takes
+    oibl_netvlad_backward, the other K of NETVLAD_CLUSTERS oibl_netvlad_backward_k."""
     dev = _need_cuda(feat, assign_w, centroids, grad_out)
     want = _want_letters("netvlad_backward", want)
     if feat.dtype != torch.float32 or grad_out.dtype != torch.float32:
@@ -699,11 +726,19 @@ def netvlad_backward(feat: torch.Tensor, assign_w: torch.Tensor, centroids: torc
     K, aw = _head_weights("netvlad_backward", assign_w, centroids, C_)
     if grad_out.numel() != N * K * C_:
         raise ValueError(f"netvlad_backward: grad_out has {grad_out.numel()} elements, expected {N} x {K * C_}")
+    general = _head_clusters("netvlad_backward", K)
     lib = _lib.load()
-    ws = workspace(lib.oibl_netvlad_backward_workspace_bytes(N, P, K, C_, int("x" in want)), dev, "netvlad_backward")
     gw = torch.empty((K, C_), dtype=torch.float32, device=dev) if "w" in want else None
     gc = torch.empty((K, C_), dtype=torch.float32, device=dev) if "c" in want else None
     gx = torch.empty(feat.shape, dtype=torch.float32, device=dev) if "x" in want else None
+    if general:
+        ws = workspace(lib.oibl_netvlad_k_backward_workspace_bytes(N, P, K, C_, int("x" in want)), dev,
+                       "netvlad_backward_k")
+        _lib.check(lib.oibl_netvlad_backward_k(_ptr(feat), N, P, K, C_, _ptr(aw), _ptr(centroids),
+                                               int(normalize_input), _ptr(grad_out), _ptr(gw), _ptr(gc), _ptr(gx),
+                                               _ptr(ws), ws.numel(), _stream(dev)), "netvlad_backward_k")
+        return gw, gc, gx
+    ws = workspace(lib.oibl_netvlad_backward_workspace_bytes(N, P, K, C_, int("x" in want)), dev, "netvlad_backward")
     _lib.check(lib.oibl_netvlad_backward(_ptr(feat), N, P, K, C_, F32, _ptr(aw), _ptr(centroids),
                                          int(normalize_input), _ptr(grad_out), _ptr(gw), _ptr(gc), _ptr(gx),
                                          _ptr(ws), ws.numel(), _stream(dev)), "netvlad_backward")
@@ -725,7 +760,8 @@ def netvlad_head(feat: torch.Tensor, assign_w: torch.Tensor, centroids: torch.Te
     """The differentiable descriptor head: vlad_norm [N][K*C], bit-equal to `netvlad(..., want_norm=True)`, with a
     graph to whichever of feat, assign_w ([K][C] or conv.weight's [K][C][1][1]) and centroids require a gradient;
     its backward is one call of `netvlad_backward` for exactly those.  A bf16 map is widened to fp32 first (the
-    gradient kernels are fp32); its gradient then comes back in bf16 through torch's cast."""
+    gradient kernels are fp32); its gradient then comes back in bf16 through torch's cast.  K as in `netvlad`: 64 on
+    the tuned kernels, the other multiples of 16 up to 128 on the K-general ones, anything else a ValueError."""
     if feat.dtype == torch.bfloat16:
         feat = feat.float()
     _need_cuda(feat, assign_w, centroids)
