@@ -1,7 +1,8 @@
 // The f16mx stem for float32 NCHW input as a 12-wave kernel of its own (included by stem.hip, inside namespace oibl,
-// behind vgg_stem_x3_kernel whose constants, parameters and helpers it uses).
+// behind stem_parts.h, whose parts it shares with the 16-wave kernel vgg_stem_mx_kernel of stem_mx16.h: formats,
+// roles and numerics are described there).
 //
-// vgg_stem_x3_kernel<true> gives a consumer wave 32 output channels x 64 pixels: per tap 12 ds_read_b128 for 6 matrix
+// vgg_stem_mx_kernel gives a consumer wave 32 output channels x 64 pixels: per tap 12 ds_read_b128 for 6 matrix
 // instructions — every pixel fragment is read once per output-channel half, every weight fragment by all four
 // waves — and the four consumers are bound by the LDS port, not by the matrix pipe.  Here a consumer
 // wave holds BOTH output-channel halves of its 64 pixels (64 accumulators): per tap 8 weight reads + 8 pixel reads
@@ -24,8 +25,8 @@
 // sequence (mid A, end A, mid B, end B) in both roles; nothing that is conditional skips a barrier.
 //
 // Numerics: every output element accumulates its taps of input half 0, then of half 1, in tap order, f16 slot 0, f16
-// slot 1, scaled e2m3 — the order of stages S1, S2 of vgg_stem_x3_kernel<true>; pooling, bias, clamp, mx_pack_half and
-// the stores are its per-element operations: the lines are bit-identical (tests/test_gpu_stem_mx12.py).
+// slot 1, scaled e2m3 — the order of stages S1, S2 of vgg_stem_mx_kernel; pooling, bias, clamp, mx_pack_half and
+// the stores are the same functions (stem_parts.h): the lines are bit-identical (tests/test_gpu_stem_mx12.py).
 constexpr int M12_PROD = 8;                 // producer waves
 constexpr int M12_BARRIERS_PER_TILE = 4;    // mid A, end A, mid B, end B
 constexpr int M12_LO_TAPS = 5;              // taps 0-4: refilled behind the mid barrier; taps 5-8 at the head of a stage
@@ -35,130 +36,47 @@ __global__ __launch_bounds__(64 * (4 + M12_PROD)) void stem_mx12_kernel(StemPara
   char* const wl = smem;                 // [tap][output half c][32 rows][f16mx line of the stage's input half]
   char* const hb = smem + S3_W_BYTES;    // halo buffer h: channels 32h..32h+31 of the current tile
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  // tiles of this workgroup: XCD x owns a contiguous eighth of the tile sequence (see vgg_stem_x3_kernel)
-  int first = blockIdx.x, stride = gridDim.x, tile_end = p.ntiles;
-  if ((gridDim.x & 7) == 0) {
-    const int x = blockIdx.x & 7;
-    stride = gridDim.x >> 3;
-    first = (int)((long)p.ntiles * x / 8) + (int)(blockIdx.x >> 3);
-    tile_end = (int)((long)p.ntiles * (x + 1) / 8);
-  }
-  int niter = 0;
-  if (first < tile_end) niter = (tile_end - first + stride - 1) / stride;
+  const StemTiles tiles = stem_xcd_tiles(p.ntiles);
+  const int first = tiles.first, stride = tiles.stride, niter = tiles.niter;
   const int Ho = p.H >> 1, Wo = p.W >> 1;
-  if (threadIdx.x < 64) reinterpret_cast<float*>(smem + S3_BIAS_OFF)[threadIdx.x] = p.b1[threadIdx.x] * p.act_scale;
-  if (threadIdx.x >= 64 && threadIdx.x < 128)
-    reinterpret_cast<float*>(smem + S3_BIAS_OFF)[threadIdx.x] = p.b2[threadIdx.x - 64] * p.act_scale;
-  __syncthreads();
-  float range_seen = 0.f;
-  auto raise_if_out_of_range = [&]() __attribute__((always_inline)) {
-    if (__builtin_amdgcn_ballot_w64(range_seen >= 65504.f) != 0) {
-      if (range_seen >= 65504.f) mx_raise_range_flag(p.range_flag);
-    }
-  };
+  stem_bias_to_lds(smem, p.b1, p.b2, p.act_scale);
+  float range_seen = 0.f;   // (mx_raise_if_out_of_range)
   using H0 = std::integral_constant<int, 0>;
   using H1 = std::integral_constant<int, 1>;
 
   if (wave >= 4) {
     // ================================ producers (waves 4-11) ====================================
-    // The producer code of vgg_stem_x3_kernel<true, false> — gather as nine rows of three pixels, conv1_1 in split
-    // bf16, half-line packing, the conflict-free lane -> pixel map — over one or two blocks per wave.
+    // The producers' parts of stem_parts.h — gather as nine rows of three pixels, conv1_1 in split bf16, half-line
+    // packing, the conflict-free lane -> pixel map — over one or two blocks per wave.
     // (the lane id is made inside each role: a value computed in front of the role split stays live through both)
     const int lane = fresh_lane_id(), half = lane >> 5, l31 = lane & 31;
     const int pprio = p.prod_prio & 3;
-    if (pprio == 1) __builtin_amdgcn_s_setprio(1);
-    else if (pprio == 2) __builtin_amdgcn_s_setprio(2);
-    else if (pprio == 3) __builtin_amdgcn_s_setprio(3);
+    stem_raise_prio(pprio);
     const int pw = wave - 4;                                  // 0..7
     const int nb = pw + M12_PROD < ST_BLOCKS ? 2 : 1;         // blocks pw and (waves 0-2) pw + 8 of the 11
     const __amdgpu_buffer_rsrc_t rs_x =
         __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.x), 0, (int)p.x_bytes, 0x00020000);
     bf16x8_t wh[2][2], wlo[2][2];
-#pragma unroll
-    for (int s = 0; s < 2; ++s)
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const int idx = 8 * s + e;
-        const int k = idx < (half ? 12 : 15) ? (idx / 3 + (half ? 5 : 0)) * 3 + idx % 3 : 27;
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-          const int ch = 16 * ((l31 >> 2) & 1) + 4 * (l31 >> 3) + (l31 & 3);   // channel of row l31
-          const float v = k < 27 ? p.w1[(32 * h + ch) * 27 + k] * p.act_scale : 0.f;
-          uint16_t hi, lo;
-          x3_split(v, hi, lo);
-          wh[h][s][e] = (short)hi;
-          wlo[h][s][e] = (short)lo;
-        }
-      }
+    stem_w1_fragments<K_ROWS, true>(p.w1, p.act_scale, half, l31, wh, wlo);
     const float* const bias_l = reinterpret_cast<const float*>(smem + S3_BIAS_OFF) + 16 * half;
-    const int plane = p.H * p.W;
-    const int lpix = 2 * (l31 & 7) + ((l31 >> 3) & 1) + 16 * (l31 >> 4);
+    const int lpix = mx_lane_pixel(l31);
     auto row_of = [&](int bi) __attribute__((always_inline)) { return 32 * (pw + M12_PROD * bi) + lpix; };
-    auto hyx_of = [&](int bi, int& hy, int& hx) __attribute__((always_inline)) {
-      const int r = row_of(bi), rc = r < ST_HALO_PX ? r : ST_HALO_PX - 1;
-      hy = rc / C64_HW;
-      hx = rc - hy * C64_HW;
-    };
     int g_swz[2], g_rel[2];
 #pragma unroll
     for (int bi = 0; bi < 2; ++bi) {
       int hy, hx;
-      hyx_of(bi, hy, hx);
+      stem_halo_yx(row_of(bi), hy, hx);
       g_swz[bi] = c64_swz(hy, hx);
       g_rel[bi] = hy * p.W + hx;
     }
-    auto decode = [&](int tile, int& n, int& ty, int& tx) __attribute__((always_inline)) {
-      const unsigned r2 = (unsigned)tile / (unsigned)p.tiles_x;
-      tx = tile - (int)r2 * p.tiles_x;
-      n = (int)(r2 / (unsigned)p.tiles_y);
-      ty = (int)r2 - n * p.tiles_y;
-    };
-    auto is_interior = [&](int ty, int tx) __attribute__((always_inline)) {
-      return ty >= 1 && ty * 8 + 10 <= p.H && tx >= 1 && tx * 32 + 34 <= p.W;
-    };
     float xv[2][16];
     int xfix[2] = {0, 0};   // image edge: 1 = this pixel's rows were fetched from x (not x - 1), 2 = from x - 2
     auto issue_loads = [&](int tile) __attribute__((always_inline)) {
-      int n, ty, tx;
-      decode(tile, n, ty, tx);
-      const int y0 = ty * 8 - 1, x0 = tx * 32 - 1;
-      const int origin = ((n * 3) * p.H + y0) * p.W + x0;
-      const bool interior = is_interior(ty, tx);
+      const StemTile t = stem_tile(p, tile);
 #pragma unroll
       for (int bi = 0; bi < 2; ++bi) {
         if (bi >= nb) continue;   // wave-uniform
-        bool in = true, ya = true, yc = true;
-        int shift = -1;
-        xfix[bi] = 0;
-        if (!interior) {
-          int hy, hx;
-          hyx_of(bi, hy, hx);
-          const int y = y0 + hy, x = x0 + hx;
-          in = y >= 0 && y < p.H && x >= 0 && x < p.W;
-          ya = y > 0;
-          yc = y + 1 < p.H;
-          xfix[bi] = !in ? 0 : x == 0 ? 1 : x + 1 >= p.W ? 2 : 0;
-          shift = xfix[bi] == 1 ? 0 : xfix[bi] == 2 ? -2 : -1;
-        }
-        const int base = origin + g_rel[bi] + shift;
-#pragma unroll
-        for (int i = 0; i < 5; ++i) {
-          const int rA = i, rB = i + 5 < 9 ? i + 5 : 8;
-          const int oA = (rA / 3) * plane + (rA % 3 - 1) * p.W, oB = (rB / 3) * plane + (rB % 3 - 1) * p.W;
-          const int kyA = rA % 3, kyB = rB % 3;
-          unsigned off = (unsigned)(base + (half ? oB : oA)) * 4u;
-          if (!interior) {
-            const int ky = half ? kyB : kyA;
-            const bool ok = in && (ky == 0 ? ya : ky == 2 ? yc : true);
-            off = ok ? off : ST_OOB;
-          }
-          const auto d = __builtin_amdgcn_raw_buffer_load_b96(rs_x, (int)off, 0, 0);
-          const unsigned d0 = d[0], d1 = d[1], d2 = d[2];
-          xv[bi][3 * i] = __builtin_bit_cast(float, d0);
-          xv[bi][3 * i + 1] = __builtin_bit_cast(float, d1);
-          xv[bi][3 * i + 2] = __builtin_bit_cast(float, d2);
-        }
-        xv[bi][15] = 0.f;
+        xfix[bi] = mx_gather_rows(rs_x, p, t, row_of(bi), g_rel[bi], half, xv[bi]);
       }
     };
     bf16x8_t xh[2][2], xl[2][2];
@@ -172,33 +90,11 @@ __global__ __launch_bounds__(64 * (4 + M12_PROD)) void stem_mx12_kernel(StemPara
           xl[bi][s][e] = 0;
         }
     auto convert = [&]() __attribute__((always_inline)) {
-      typedef __attribute__((ext_vector_type(4))) uint32_t u32x4_t;
 #pragma unroll
       for (int bi = 0; bi < 2; ++bi) {
         if (bi >= nb) continue;
-        if (__builtin_amdgcn_ballot_w64(xfix[bi] != 0) != 0) {   // an image edge inside this block (rare)
-          const bool left = xfix[bi] == 1, right = xfix[bi] == 2;
-#pragma unroll
-          for (int i = 0; i < 5; ++i) {
-            const float a = xv[bi][3 * i], b = xv[bi][3 * i + 1], c = xv[bi][3 * i + 2];
-            xv[bi][3 * i] = left ? 0.f : right ? b : a;
-            xv[bi][3 * i + 1] = left ? a : right ? c : b;
-            xv[bi][3 * i + 2] = left ? b : right ? 0.f : c;
-          }
-        }
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-          u32x4_t hi4, lo4;
-#pragma unroll
-          for (int e2 = 0; e2 < 4; ++e2) {
-            uint32_t hi, lo;
-            x3_split_pair(xv[bi][8 * s + 2 * e2], xv[bi][8 * s + 2 * e2 + 1], hi, lo);
-            hi4[e2] = hi;
-            lo4[e2] = lo;
-          }
-          xh[bi][s] = __builtin_bit_cast(bf16x8_t, hi4);
-          xl[bi][s] = __builtin_bit_cast(bf16x8_t, lo4);
-        }
+        mx_edge_fix(xv[bi], xfix[bi]);
+        x3_split_window(xv[bi], xh[bi], xl[bi]);
       }
     };
     // conv1_1 of channel half h on block bi, bias + clamp + half-line packing, halo lines -> LDS.  bi is a RUN-TIME,
@@ -209,64 +105,19 @@ __global__ __launch_bounds__(64 * (4 + M12_PROD)) void stem_mx12_kernel(StemPara
     // instead (8 v_mov_b64 per block, 8 more on block 1) measured no better: producer work 12.7-12.8k against 12.5-12.6k ticks
     // per tile, the launch 1.31 against 1.29 ms (profiles/stem_mx12_ab.txt).
     auto produce_one = [&](int tile, auto h_c, int bi, char* buf) __attribute__((always_inline)) {
-      typedef __attribute__((ext_vector_type(4))) unsigned u4;
-      typedef __attribute__((ext_vector_type(3))) unsigned u3;
       constexpr int h = decltype(h_c)::value;
-      int n, ty, tx;
-      decode(tile, n, ty, tx);
-      const int y0 = ty * 8 - 1, x0 = tx * 32 - 1;
-      const bool interior = is_interior(ty, tx);
+      const StemTile t = stem_tile(p, tile);
       const bf16x8_t bh0 = bi ? xh[1][0] : xh[0][0], bh1 = bi ? xh[1][1] : xh[0][1];
       const bf16x8_t bl0 = bi ? xl[1][0] : xl[0][0], bl1 = bi ? xl[1][1] : xl[0][1];
       f32x16_t acc;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const float4 b = *reinterpret_cast<const float4*>(bias_l + 32 * h + 4 * j);
-        acc[4 * j] = b.x;
-        acc[4 * j + 1] = b.y;
-        acc[4 * j + 2] = b.z;
-        acc[4 * j + 3] = b.w;
-      }
-      __builtin_amdgcn_s_setprio(3);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wlo[h][0], bh0, acc, 0, 0, 0);   // the order of conv1_1_mfma_kernel<X3>
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh[h][0], bl0, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh[h][0], bh0, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wlo[h][1], bh1, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh[h][1], bl1, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh[h][1], bh1, acc, 0, 0, 0);
-      if (pprio == 0) __builtin_amdgcn_s_setprio(0);
-      else if (pprio == 1) __builtin_amdgcn_s_setprio(1);
-      else if (pprio == 2) __builtin_amdgcn_s_setprio(2);
-      bool pix_ok = true;
-      if (!interior) {   // border tiles only: is this halo pixel inside the image?
-        int hy, hx;
-        hyx_of(bi, hy, hx);
-        const int y = y0 + hy, x = x0 + hx;
-        pix_ok = y >= 0 && y < p.H && x >= 0 && x < p.W;
-      }
-      // ReLU, the fp16 bound and conv1_2's zero padding (a halo pixel outside the image) in ONE v_med3
-      float c[16];
-      const float lim = pix_ok ? 65504.f : 0.f;
-#pragma unroll
-      for (int j = 0; j < 16; ++j) c[j] = __builtin_amdgcn_fmed3f(acc[j], 0.f, lim);
-      unsigned ph16[8], ph6[3], pl6[3], pbh, pbl;
-      mx_pack_half<false>(c, ph16, ph6, pl6, pbh, pbl, range_seen);
+      stem_bias16(bias_l + 32 * h, 4, acc);
+      acc = conv1_1_sextet(wh[h], wlo[h], bh0, bh1, bl0, bl1, acc);
+      stem_restore_prio(pprio);
       const int r = row_of(bi);
-      if (r < ST_HALO_PX) {   // (block 10 has 12 surplus lanes)
-        char* row = buf + r * 128;
-        const int sw = bi ? g_swz[1] : g_swz[0];
-        *reinterpret_cast<u4*>(row + (((2 * half) ^ sw) << 4)) = (u4){ph16[0], ph16[1], ph16[2], ph16[3]};
-        *reinterpret_cast<u4*>(row + (((2 * half + 1) ^ sw) << 4)) = (u4){ph16[4], ph16[5], ph16[6], ph16[7]};
-        if (half == 0) {
-          *reinterpret_cast<u3*>(row + ((4 ^ sw) << 4)) = (u3){ph6[0], ph6[1], ph6[2]};
-          *reinterpret_cast<u3*>(row + ((5 ^ sw) << 4)) = (u3){pl6[0], pl6[1], pl6[2]};
-        } else {
-          *reinterpret_cast<unsigned*>(row + ((4 ^ sw) << 4) + 12) = ph6[0];
-          *reinterpret_cast<unsigned*>(row + ((5 ^ sw) << 4) + 12) = pl6[0];
-          *reinterpret_cast<u4*>(row + ((6 ^ sw) << 4)) = (u4){ph6[1], ph6[2], 0u, pbh};
-          *reinterpret_cast<u4*>(row + ((7 ^ sw) << 4)) = (u4){pl6[1], pl6[2], 0u, pbl};
-        }
-      }
+      MxHalfLine L;
+      mx_clamp_pack_half(acc, stem_halo_pixel_in_image(p, t, r), L, range_seen);
+      if (r < ST_HALO_PX)   // (block 10 has 12 surplus lanes)
+        mx_write_half_line(buf + r * 128, bi ? g_swz[1] : g_swz[0], half, L);
     };
     // conv1_2's weights: LDS row (tap * 2 + c) * 32 + m = the f16mx line of output channel 32 c + chan(m), the stage's
     // input group; 16-byte slots swizzled by (m >> 1) & 7.  One LDS-DMA instruction fills 8 rows; piece 4 j + k holds
@@ -339,11 +190,7 @@ __global__ __launch_bounds__(64 * (4 + M12_PROD)) void stem_mx12_kernel(StemPara
       constexpr int MIDPOS = decltype(midpos_c)::value;
       if (MID) stream_w(decltype(h_c)::value ^ 1, std::false_type{});
       bool late_interior = false;
-      if (late_tile >= 0) {
-        int n, ty, tx;
-        decode(late_tile, n, ty, tx);
-        late_interior = is_interior(ty, tx);
-      }
+      if (late_tile >= 0) late_interior = stem_tile(p, late_tile).interior;
       int nblk = 2;
       asm volatile("" : "+s"(nblk));   // (a run-time trip count: the loop stays a loop)
 #pragma unroll 1
@@ -393,22 +240,15 @@ __global__ __launch_bounds__(64 * (4 + M12_PROD)) void stem_mx12_kernel(StemPara
       p.prof[6] = 0;
       p.prof[7] = 0;
     }
-    raise_if_out_of_range();
+    mx_raise_if_out_of_range(range_seen, p.range_flag);
     return;
   }
 
   // ================================== consumers (waves 0-3) =====================================
-  typedef __attribute__((ext_vector_type(4))) unsigned u4;
-  typedef __attribute__((ext_vector_type(2))) unsigned u2;
-  typedef __attribute__((ext_vector_type(4))) int i4;
+  typedef stem_u4 u4;
   const int lane = fresh_lane_id(), half = lane >> 5, l31 = lane & 31;
-  {
-    const int cprio = (p.prod_prio >> 2) & 3;
-    if (cprio == 1) __builtin_amdgcn_s_setprio(1);
-    else if (cprio == 2) __builtin_amdgcn_s_setprio(2);
-    else if (cprio == 3) __builtin_amdgcn_s_setprio(3);
-  }
-  // pixel (B) fragment addressing: that of vgg_stem_x3_kernel<true>
+  stem_raise_prio((p.prod_prio >> 2) & 3);
+  // pixel (B) fragment addressing: stem_pixel_addressing, mx_weight_row
   // LDS addresses are kept as INTEGERS and turned into pointers at the read (as pointers every read pays a v_add of
   // the — zero — base of the dynamic allocation: on a SIMD whose vector ALU the producers fill, each vector instruction
   // of the consumers is time).  The kernel has no static LDS: smem starts the allocation, and its base — part of every
@@ -417,16 +257,9 @@ __global__ __launch_bounds__(64 * (4 + M12_PROD)) void stem_mx12_kernel(StemPara
   const int lds0 = (int)(size_t)(lds_t)smem;
   auto at = [&](int a, int off) __attribute__((always_inline)) { return (lds_t)(size_t)(unsigned)a + off; };
   int e_kx[3], pxb;
-  {
-    const int ly = 2 * wave + ((l31 >> 1) & 1);
-    const int lx = 2 * (l31 >> 2) + (l31 & 1);
-    const int fix = half ^ ((ly & 1) << 2);
-    e_kx[0] = (fix ^ ((lx >> 1) & 7)) << 4;
-    e_kx[2] = (fix ^ (((lx >> 1) + 1) & 7)) << 4;
-    e_kx[1] = (lx & 1) ? e_kx[2] : e_kx[0];
-    pxb = lds0 + (ly * C64_HW + lx) * 128;
-  }
-  const int w_base = lds0 + l31 * 128 + ((half ^ ((l31 >> 1) & 7)) << 4);
+  stem_pixel_addressing(wave, half, l31, e_kx, pxb);
+  pxb += lds0;
+  const int w_base = lds0 + mx_weight_row(half, l31);
   __builtin_amdgcn_s_barrier();
   const bool cprof = p.prof != nullptr && blockIdx.x == 0 && wave == 0;
   unsigned long long ct[3] = {0, 0, 0}, c0 = cprof ? __builtin_amdgcn_s_memtime() : 0;
@@ -463,7 +296,7 @@ __global__ __launch_bounds__(64 * (4 + M12_PROD)) void stem_mx12_kernel(StemPara
       return (ky * C64_HW + kx) * 128 + i * 2048;
     };
     auto waddr = [&](int kk) __attribute__((always_inline)) {
-      int a = w_base;   // (volatile: ONE live register for the four slot addresses, as in vgg_stem_x3_kernel<true>)
+      int a = w_base;   // (volatile: ONE live register for the four slot addresses: mx_weight_row)
       if (kk) asm volatile("v_xor_b32 %0, %1, %2" : "=v"(a) : "s"(kk << 5), "v"(w_base));
       return a;
     };
@@ -488,12 +321,7 @@ __global__ __launch_bounds__(64 * (4 + M12_PROD)) void stem_mx12_kernel(StemPara
       acc[c][i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(w1[c], b1[i], acc[c][i], 0, 0, 0);
     };
     auto mx = [&](int c, int i) __attribute__((always_inline)) {
-      // e2m3 x e2m3 (cbsz = blgp = 2): registers 0-5 of either operand; its scale: byte 0 of register 7
-      const i32x8_t a8 = __builtin_shufflevector(__builtin_bit_cast(i4, wma[c]), __builtin_bit_cast(i4, wmt[c]),
-                                                 0, 1, 2, 3, 4, 5, 6, 7);
-      const i32x8_t b8 = __builtin_shufflevector(__builtin_bit_cast(i4, bma[i]), __builtin_bit_cast(i4, bmt[i]),
-                                                 0, 1, 2, 3, 4, 5, 6, 7);
-      acc[c][i] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a8, b8, acc[c][i], 2, 2, 0, a8[7], 0, b8[7]);
+      acc[c][i] = mx_scaled_mfma(wma[c], wmt[c], bma[i], bmt[i], acc[c][i]);
     };
 #define M12_SB() __builtin_amdgcn_sched_barrier(0)
     {
@@ -600,12 +428,9 @@ __global__ __launch_bounds__(64 * (4 + M12_PROD)) void stem_mx12_kernel(StemPara
     stage(H0{});
     stage(H1{});
     const unsigned long long e0 = cprof ? __builtin_amdgcn_s_memtime() : 0;
-    // 2x2 max-pool (two DPP steps over the lane quad), bias, clamp, pack, store: the epilogue of
-    // vgg_stem_x3_kernel<true>, once per output-channel half
-    const int tile = first + it * stride;
-    const unsigned r2 = (unsigned)tile / (unsigned)p.tiles_x;
-    const int tx = tile - (int)r2 * p.tiles_x;
-    const int n = (int)(r2 / (unsigned)p.tiles_y), ty = (int)r2 - n * p.tiles_y;
+    // mx_pooled_epilogue, once per output-channel half
+    int n, ty, tx;
+    stem_decode(p, first + it * stride, n, ty, tx);
     const int oy = ty * 4 + wave;
     const int lane_e = fresh_lane_id();
     const int half = lane_e >> 5, l31 = lane_e & 31;   // (shadow the kernel's: nothing lane-derived stays live across the stages)
@@ -621,44 +446,7 @@ __global__ __launch_bounds__(64 * (4 + M12_PROD)) void stem_mx12_kernel(StemPara
     for (int cz = 0; cz < 2; ++cz) {
       __builtin_amdgcn_sched_barrier(0);   // (one output half at a time: interleaved, the two epilogues spill)
       const float* const bias2 = reinterpret_cast<const float*>(smem + S3_BIAS_OFF) + 64 + 32 * cz + 16 * half;
-      float bv[16];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const float4 b = *reinterpret_cast<const float4*>(bias2 + 4 * j);
-        bv[4 * j] = b.x;
-        bv[4 * j + 1] = b.y;
-        bv[4 * j + 2] = b.z;
-        bv[4 * j + 3] = b.w;
-      }
-      float v[16], m0[16], m1[16];
-      const bool odd = l31 & 1;
-#pragma unroll
-      for (int j = 0; j < 16; ++j) {
-        asm volatile("v_max_f32_dpp %0, %1, %1 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf" : "=v"(m0[j]) : "v"(acc[cz][0][j]));
-        asm volatile("v_max_f32_dpp %0, %1, %1 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf" : "=v"(m1[j]) : "v"(acc[cz][1][j]));
-      }
-#pragma unroll
-      for (int j = 0; j < 16; ++j) v[j] = odd ? m1[j] : m0[j];
-#pragma unroll
-      for (int j = 0; j < 16; ++j)   // (s_nop: the select above may be scheduled right in front of its reader)
-        asm volatile("s_nop 1\n\tv_max_f32_dpp %0, %1, %1 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf" : "=v"(m0[j]) : "v"(v[j]));
-#pragma unroll
-      for (int j = 0; j < 16; ++j) v[j] = __builtin_amdgcn_fmed3f(m0[j] + bv[j], 0.f, f16max);   // bias, ReLU, the fp16 bound
-      unsigned h16[8], h6[3], l6[3], bh, bl;
-      mx_pack_half<false>(v, h16, h6, l6, bh, bl, range_seen);
-      // lanes 0, 1 of a quad store: pooled pixel 8 (l31 & 1) + (l31 >> 2) of the tile row
-      const unsigned off = (l31 & 2) ? 0x80000000u
-                                     : (unsigned)(tx * 16 + 8 * (l31 & 1) + (l31 >> 2)) * 256u + (unsigned)cz * 128u;
-      __builtin_amdgcn_raw_buffer_store_b128((u4){h16[0], h16[1], h16[2], h16[3]}, rs_o, (int)(off + 32 * half), 0, 0);
-      __builtin_amdgcn_raw_buffer_store_b128((u4){h16[4], h16[5], h16[6], h16[7]}, rs_o, (int)(off + 32 * half + 16), 0, 0);
-      const unsigned oa = off + (half ? 76u : 64u), ob = off + (half ? 96u : 68u);
-      __builtin_amdgcn_raw_buffer_store_b32(h6[0], rs_o, (int)oa, 0, 0);
-      __builtin_amdgcn_raw_buffer_store_b64((u2){h6[1], h6[2]}, rs_o, (int)ob, 0, 0);
-      __builtin_amdgcn_raw_buffer_store_b32(l6[0], rs_o, (int)(oa + 16), 0, 0);
-      __builtin_amdgcn_raw_buffer_store_b64((u2){l6[1], l6[2]}, rs_o, (int)(ob + 16), 0, 0);
-      const unsigned ot = half ? off + 104u : 0x80000000u;   // the tails' zero dword + scale byte
-      __builtin_amdgcn_raw_buffer_store_b64((u2){zero, bh}, rs_o, (int)ot, 0, 0);
-      __builtin_amdgcn_raw_buffer_store_b64((u2){zero, bl}, rs_o, (int)(ot + 16), 0, 0);
+      mx_pooled_epilogue(acc[cz][0], acc[cz][1], bias2, f16max, zero, rs_o, tx, cz, half, l31, range_seen);
     }
     if (cprof) {
       const unsigned long long e1 = __builtin_amdgcn_s_memtime();
@@ -672,5 +460,5 @@ __global__ __launch_bounds__(64 * (4 + M12_PROD)) void stem_mx12_kernel(StemPara
     p.prof[2] = ct[2];   // epilogue
     p.prof[3] = 0;
   }
-  raise_if_out_of_range();
+  mx_raise_if_out_of_range(range_seen, p.range_flag);
 }

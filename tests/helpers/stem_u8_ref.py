@@ -1,4 +1,4 @@
-"""References and case makers for the three uint8 stems of csrc/stem.hip run alone (tests/test_gpu_stem_u8.py, and
+"""References and case makers for the three uint8 stems launched by csrc/stem.hip run alone (tests/test_gpu_stem_u8.py, and
 tests/test_stem_u8_ref_cpu.py for what can be said without a GPU):
 
   * `fma_normalise`: the exact input of the bf16x3 / f16mx stems — ToTensor + Normalize as ONE fma per value,

@@ -1,5 +1,5 @@
 """The 12-wave f16mx stem (csrc/stem_mx12.h: 64 output channels x 64 pixels per consumer wave, weights refilled by
-tap group) against the 16-wave kernel it replaces on the float32-input route (vgg_stem_x3_kernel<true>, selected by
+tap group) against the 16-wave kernel it replaces on the float32-input route (vgg_stem_mx_kernel<false> of csrc/stem_mx16.h, selected by
 the debug library's oibl_debug_set_stem_mx12(0)): the same seeded inputs through both, the raw int32 lines compared
 with torch.equal — every output element accumulates the same products in the same order, so nothing may differ —
 and the range flag raised by exactly the same inputs (oibl_debug_set_stem_mx_flag hands the entry point a flag)."""

@@ -1,9 +1,9 @@
-"""The three uint8 stems of csrc/stem.hip run ALONE (oibl_debug_vgg16_stem_u8 of the debug library), not judged twelve
+"""The three uint8 stems launched by csrc/stem.hip run ALONE (oibl_debug_vgg16_stem_u8 of the debug library), not judged twelve
 layers later as tests/test_gpu_u8.py and tests/test_gpu_descriptor.py judge them:
 
-  bf16    vgg_stem_kernel<true>             3 x 257 table of bf16((u / 255 - mean) / std)
-  bf16x3  vgg_stem_x3_kernel<false, true>   v = fmaf(u, a_c, b_c), 12-byte dword-aligned gathers, K order (ky, kx, c)
-  f16mx   vgg_stem_x3_kernel<true, true>    the same producers in front of the f16mx consumers
+  bf16    vgg_stem_kernel<true>     (stem_bf16.h)  3 x 257 table of bf16((u / 255 - mean) / std)
+  bf16x3  vgg_stem_x3_kernel<true>  (stem_x3.h)    v = fmaf(u, a_c, b_c), 12-byte dword-aligned gathers, K order (ky, kx, c)
+  f16mx   vgg_stem_mx_kernel<true>  (stem_mx16.h)  the same producers (stem_parts.h) in front of the f16mx consumers
 
 against the emulation of their arithmetic and the fp64 convolutions of the exact input (tests/helpers/stem_u8_ref.py;
 the references alone are held to the same bars in tests/test_stem_u8_ref_cpu.py), and bit for bit against themselves:
@@ -74,7 +74,7 @@ def _weights_of(r):
 @pytest.mark.parametrize("act_scale", [1.0, MX_ACT_SCALE], ids=["scale1", "scale2^-3"])
 @pytest.mark.parametrize("kind,shape", CASES, ids=_id)
 def test_f16mx_lines_against_the_emulation_and_fp64(dev, kind, shape, act_scale):
-    """The lines of vgg_stem_x3_kernel<true, true> carry what helpers/mx_emul.stem computes from fma_normalise(u8) —
+    """The lines of vgg_stem_mx_kernel<true> carry what helpers/mx_emul.stem computes from fma_normalise(u8) —
     the bar of the float32 route against the same emulation — and lie within the bars of test_vgg_stem_mx_fused of the
     fp64 convolutions; they are well-formed lines; the range flag stays 0.  At the production activation scale 2^-3
     (conv1_1's weights and both biases scaled, every line stored scaled) the joined lines times 8 meet the same bars.
@@ -109,7 +109,7 @@ def test_f16mx_lines_against_the_emulation_and_fp64(dev, kind, shape, act_scale)
 # ---- B (and F): bf16x3 ---------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("kind,shape", CASES, ids=_id)
 def test_bf16x3_against_fp64_and_the_float32_route(dev, kind, shape):
-    """vgg_stem_x3_kernel<false, true> against the fp64 convolutions of fma_normalise(u8) (the bar of
+    """vgg_stem_x3_kernel<true> against the fp64 convolutions of fma_normalise(u8) (the bar of
     test_vgg_stem_x3_fused), and per output pixel against ops.vgg16_stem_x3 on fma_normalise(u8): the same sums in
     another order inside conv1_1.  Measured values: module docstring."""
     r = R.reference(kind, shape)

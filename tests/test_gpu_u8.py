@@ -1,5 +1,5 @@
 """Raw uint8 NHWC input of the 1e-4 modes: the bf16x3 / f16mx stems gather the
-loader's bytes themselves (csrc/stem.hip, vgg_stem_x3_kernel<MX, U8>) — no normalising pass, a quarter of the
+loader's bytes themselves (csrc/stem_x3.h, csrc/stem_mx16.h: vgg_stem_x3_kernel<true>, vgg_stem_mx_kernel<true>) — no normalising pass, a quarter of the
 bytes over PCIe.  Normalize is one fma per value there (within 2^-16 of the loader's three rounded operations:
 tests/test_stem_u8_cpu.py), so the result is not bit-identical to the fp32-input route; it is checked against it
 (a few 1e-6), against the oracle on the loader's own tensor (1e-4), on border-heavy odd sizes, and the old route

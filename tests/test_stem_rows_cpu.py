@@ -1,5 +1,5 @@
-"""CPU restatement of the index logic of the f16mx stem's producers (openibl_amd/csrc/stem.hip,
-vgg_stem_x3_kernel<true>): conv1_1's 3 x 3 x 3 window travels as nine ROWS (c, ky) of three consecutive
+"""CPU restatement of the index logic of the f16mx stem's producers (openibl_amd/csrc/stem_parts.h,
+mx_gather_rows / mx_edge_fix / stem_w1_fragments<K_ROWS>): conv1_1's 3 x 3 x 3 window travels as nine ROWS (c, ky) of three consecutive
 pixels — the lower lane half owns rows 0-4, the upper half rows 5-8 (and row 8 once more under zero weights) —
 and K slot idx = 8 s + e of a half is element kx = idx % 3 of its row idx / 3.  At the image's left / right
 edge the 12-byte fetch starts one pixel later / earlier and the elements are moved into place.  This test

@@ -1,4 +1,4 @@
-"""uint8 input of the bf16x3 / f16mx stems (csrc/stem.hip, vgg_stem_x3_kernel<MX, U8>), the parts that can be
+"""uint8 input of the bf16x3 / f16mx stems (csrc/stem_parts.h: u8_gather_rows, u8_convert, stem_w1_fragments<K_BYTES>), the parts that can be
 checked without a GPU:
 
 1. Normalize as ONE fma, v = u * a_c + b_c, against the loader's three rounded fp32 operations
@@ -70,7 +70,7 @@ def _perm(s0, s1, sel):
 
 def _lane_slots(img, y, x, half):
     """What one producer lane (halo pixel (y, x) inside the image) hands conv1_1: 16 bytes in slot order, and
-    the 27-bit validity mask, following vgg_stem_x3_kernel<., true> step by step."""
+    the 27-bit validity mask, following u8_gather_rows / u8_convert step by step."""
     H, W, _ = img.shape
     flat = np.concatenate([img.reshape(-1), np.full(16, 77, dtype=np.uint8)])   # (whatever follows the tensor)
 

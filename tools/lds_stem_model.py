@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""LDS bank-conflict model of the f16mx stem (csrc/stem.hip, vgg_stem_x3_kernel<true>) after the banking rules of
+"""LDS bank-conflict model of the f16mx stem (csrc/stem_mx16.h, vgg_stem_mx_kernel) after the banking rules of
 /opt/skills/guides/MI355X_MICROARCH.md §LDS: lane groups and bank modulus per instruction, one LDS cycle per group,
 N distinct addresses on one bank within a group = N cycles.  Counts the EXTRA cycles per 8 x 32 tile and workgroup
 (what SQ_LDS_BANK_CONFLICT counts) for the consumers' fragment reads and the producers' line writes, for the layout

@@ -198,14 +198,14 @@ def traffic_table(fp, wp, prof, tag, prec):
         tot_b, tot_n, forwards = 0.0, 0, 0
         for k, (n, v, t) in fe.items():
             if not any(tag_ in k for tag_ in ("conv3x3_ring_kernel", "conv3x3_halo_kernel", "conv3x3_halo4_kernel", "mx_pack_rows_kernel", "vgg_stem_kernel",
-                                              "vgg_stem_x3_kernel", "conv3x3_igemm_kernel", "conv3x3_c64_kernel",
+                                              "vgg_stem_x3_kernel", "vgg_stem_mx_kernel", "stem_mx12_kernel", "conv3x3_igemm_kernel", "conv3x3_c64_kernel",
                                               "conv_mx_splitk_reduce_kernel", "conv_mx_splitk_reduce8_kernel",
                                               "conv_splitk_reduce_kernel")):
                 continue
             w = wr.get(k, [1, 0.0, 1])
             tot_b += 2 * v * 1024 + w[1] * 1024 * (n / max(w[0], 1))
             tot_n += n
-            if "vgg_stem" in k:
+            if "vgg_stem" in k or "stem_mx12" in k:
                 forwards += n          # one fused stem launch per forward
         if tot_n:
             name = f"{tag}_hbm_traffic_{prec}.md" if prec else f"{tag}_hbm_traffic.md"
