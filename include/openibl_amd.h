@@ -781,6 +781,47 @@ int oibl_resize_u8(const uint8_t* x_nhwc, int N, int H, int W, int H2, int W2, i
                    const float* mean3_host, const float* std3_host, void* out, void* ws, size_t ws_bytes,
                    void* stream);
 
+/* ---- baseline JPEG decoding ------------------------------------------------------------------ *
+ * Replaces `Image.open(path).convert('RGB')` of the loader (ibl/utils/data/preprocessor.py) for baseline JPEG files:
+ * from the scan's bytes to [N][H][W][3] uint8, the bits of libjpeg-turbo as Pillow uses it (csrc/jpeg.hip and
+ * csrc/jpeg_entropy.h state the arithmetic: T.81 F.2.2 entropy decoding, coef * q in int32, the "islow" integer IDCT,
+ * "fancy" h2v1 / h2v2 chroma upsampling on the cropped planes, 16-bit fixed-point YCbCr -> RGB).  Equality holds for
+ * streams whose dequantised coefficients stay inside int16, as every encoder of 8-bit images keeps them.
+ * The markers are parsed on the host (openibl_amd/jpeg.py: `parse`, `collate`); all N images have the size H x W.
+ *   scan_bytes [scan_len] uint8   the entropy-coded bytes of all images, back to back, restart markers included
+ *                                 (1 <= scan_len < 2^31).
+ *   records [N][1408] bytes       per image, 4-byte aligned:
+ *       int32 header[16]: 0 components (1 or 3); 1, 2 luma sampling factors h, v — (1,1), (2,1) or (2,2), chroma is
+ *                         (1,1); 3..5 quantisation table of each component (0..3); 6..8 its DC table (0, 1);
+ *                         9..11 its AC table (0, 1); 12 DRI, the restart interval in MCUs (0: none);
+ *                         13 the image's first row of `segments`; 14 how many rows it has;
+ *                         15 status slot: a non-zero value found by the parser (4: restart markers missing or out of
+ *                         sequence) is what status[n] reports, whatever the device finds.
+ *       uint8 qt[4][64]   the 8-bit quantisation tables in natural (row-major) order.
+ *       uint8 huff[4][272] DC table 0, DC table 1, AC table 0, AC table 1: counts[16] of the code lengths 1..16, then
+ *                         values[256] in code order (unused entries anything).
+ *     Every field is forced into its valid range on the device (other values read as the nearest valid one): a
+ *     damaged record cannot make a kernel index outside its buffers.
+ *   segments [S][2] int32         {begin, end} byte offsets into scan_bytes of every segment — a restart interval, or
+ *                                 the whole scan when DRI = 0 — image after image in decoding order; the marker
+ *                                 FF D0+(k mod 8) stands at `end` of an image's k-th segment unless it is the last.
+ *                                 Offsets beyond scan_len are clamped.  max_segments: the largest header[14].
+ *   out_nhwc [N][H][W][3] uint8, status [N] int32 (device): 0 ok, 1 a code no Huffman length matches, 2 a coefficient
+ *                                 index above 63, 3 a segment ran out of bytes, 4 a restart marker missing or wrong
+ *                                 (or bytes left in front of the marker that ends a segment).  A damaged image yields
+ *                                 the pixels of what was decoded; its batch mates are not affected.
+ * One memset and three launches, all stream-ordered and capturable: one lane per segment decodes into zeroed int16
+ * coefficients, one thread per 8 x 8 block dequantises and transforms, one thread per pixel upsamples and converts.
+ * Integer sums only, no atomics: identical bits from run to run, whatever lane served a segment.
+ * 1 <= N <= 65535, 1 <= H <= 32768, 8 <= W <= 32768, N <= S <= 2^28; otherwise OIBL_E_INVALID before anything is
+ * launched, as for a null pointer; a short or misaligned (256 bytes) workspace is OIBL_E_WORKSPACE / OIBL_E_INVALID.
+ * Workspace: int16 coef[N][3][Bh][Bw][64] with Bw = 2 ceil(W / 16), Bh = 2 ceil(H / 16), int32 segment status [S],
+ * uint8 planes[N][3][Bh * 8][Bw * 8]; oibl_jpeg_decode_workspace_bytes returns 0 for a shape the call rejects. */
+size_t oibl_jpeg_decode_workspace_bytes(int N, int H, int W, int S);
+int oibl_jpeg_decode(const uint8_t* scan_bytes, size_t scan_len, const void* records, const int32_t* segments, int S,
+                     int max_segments, int N, int H, int W, uint8_t* out_nhwc, int32_t* status, void* ws,
+                     size_t ws_bytes, void* stream);
+
 /* ---- recall counting ---------------------------------------------------------------- *
  * Replaces the per-query Python loop of evaluate_all and spatial_nms
  * (ibl/evaluators.py:132-140, 149-160).  For every query, the rank (0-based, inside the

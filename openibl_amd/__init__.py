@@ -11,6 +11,7 @@ Layout
   sharded.py       gallery-sharded top-k matching over torch.distributed (RCCL)
   augment.py       training colour jitter and PIL's bilinear resize for raw uint8 batches on the device
                    (ColorJitter, Resize, Compose)
+  jpeg.py          host side of the device JPEG decoder: marker parser, JpegBatch, DataLoader collate (ops.decode_jpeg)
   trunk_cache.py   stored pool4 maps of the training images: re-extraction with the trunk frozen (TrunkCache)
 
 The `ibl` package at the repository root re-exports these under the reference's module names so

@@ -77,10 +77,10 @@ FAST_EXTRACTION = True   # False: batch-by-batch eager launches (the cross-check
 
 
 def _extract_local(model, data_loader, vlad, pca, gpu, print_freq, rank, scales=None, store_dtype=None,
-                   use_graphs=True, input_resize=None):
+                   use_graphs=True, input_resize=None, input_decode=None):
     """Run the loader of this rank; returns the [n_local][d] descriptor matrix ON DEVICE, in
     `store_dtype` (None = float32; float16 / bfloat16 = 16-bit descriptor storage).
-    `input_resize`: as in `extract_features`.
+    `input_resize`, `input_decode`: as in `extract_features`.
 
     Embed* models take the replayed route of openibl_amd.extract (hipGraph per batch shape, batches
     alternating between two lanes, H2D on a copy stream, descriptors written straight into a
@@ -93,14 +93,18 @@ def _extract_local(model, data_loader, vlad, pca, gpu, print_freq, rank, scales=
     if FAST_EXTRACTION and scales is None and extract.fast_path_supported(model):
         return extract.extract_descriptors(model, data_loader, vlad=vlad, pca=pca, gpu=gpu,
                                            print_freq=print_freq, rank=rank, store_dtype=store_dtype,
-                                           use_graphs=use_graphs, input_resize=input_resize)
+                                           use_graphs=use_graphs, input_resize=input_resize,
+                                           input_decode=input_decode)
     resize = extract.input_resizer(input_resize)
+    decoded = []
     batch_t, data_t = _Meter(), _Meter()
     chunks = []
     end = time.time()
     with torch.no_grad():
         for i, batch in enumerate(data_loader):
             imgs = batch[0]
+            if input_decode:
+                imgs = extract.apply_input_decode(imgs, _device(gpu), decoded, extract._batch_names(batch))
             if resize is not None:
                 imgs = extract.apply_input_resize(resize, torch.as_tensor(imgs), _device(gpu))
             data_t.update(time.time() - end)
@@ -113,6 +117,7 @@ def _extract_local(model, data_loader, vlad, pca, gpu, print_freq, rank, scales=
             if (i + 1) % print_freq == 0 and rank == 0:
                 print("Extract Features: [{}/{}]\tTime {:.3f} ({:.3f})\tData {:.3f} ({:.3f})\t".format(
                     i + 1, len(data_loader), batch_t.val, batch_t.avg, data_t.val, data_t.avg))
+    extract.check_input_decode(decoded)
     if not chunks:
         return torch.empty((0, 0), device=_device(gpu))
     return torch.cat(chunks)
@@ -146,7 +151,7 @@ def _gather_all(local: torch.Tensor, sync_gather: bool, rank: int, world: int) -
 
 def extract_features(model, data_loader, dataset, print_freq=10, vlad=True, pca=None, gpu=None,
                      sync_gather=False, scales=None, store_dtype=None, use_graphs=True, trunk_cache=None,
-                     input_resize=None):
+                     input_resize=None, input_decode=None):
     """OrderedDict fname -> CPU descriptor for every item of `dataset` (evaluators.py:36-103).
     `use_graphs=False`: the two-lane route without hipGraph capture (loaders whose batch shapes rarely
     repeat; `openibl_amd.extract.MAX_CACHED_SHAPES` bounds the captured shapes kept otherwise).
@@ -156,6 +161,13 @@ def extract_features(model, data_loader, dataset, print_freq=10, vlad=True, pca=
     (`get_transformer_test(..., as_uint8=True, resize=False)`) and every batch is resized on the device right after
     it got there — the reference's Resize, PIL's bits — before it enters the usual flow.  A float32 batch raises
     ValueError.
+
+    input_decode (extension): True — the loader delivers the FILES' BYTES: a dataset `Preprocessor(..., raw=True)` and
+    `collate_fn=openibl_amd.jpeg.collate`, which parses the markers in the worker, so that item 0 of a batch is an
+    `openibl_amd.jpeg.JpegBatch` (files of one stored size per batch).  Every batch is decoded on the device right
+    after it got there (`ops.decode_jpeg`: baseline JPEG with Pillow's bits; a file the device does not decode was
+    decoded by the worker and travels as pixels), in front of `input_resize`.  The statuses are read once, when the
+    loop has ended: RuntimeError lists the damaged files.  A tensor batch raises ValueError.
 
     Each rank extracts the slice its DistributedSliceSampler yields; slices are gathered
     rank-major and truncated to len(dataset) (the wrap-around padding of the last slices).
@@ -172,7 +184,7 @@ def extract_features(model, data_loader, dataset, print_freq=10, vlad=True, pca=
         local = trunk_cache.descriptors(model, vlad, store_dtype, pca)
     else:
         local = _extract_local(model, data_loader, vlad, pca, gpu, print_freq, rank, scales, store_dtype, use_graphs,
-                               input_resize)
+                               input_resize, input_decode)
     allf = _gather_all(local, sync_gather, rank, world)[: len(dataset)]
     features = OrderedDict()
     for item, row in zip(dataset, allf):

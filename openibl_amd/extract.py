@@ -586,15 +586,57 @@ def apply_input_resize(resize, imgs: torch.Tensor, dev) -> torch.Tensor:
     return resize(imgs.contiguous().to(dev, non_blocking=True))
 
 
+def apply_input_decode(batch0, dev, pending, names=None) -> torch.Tensor:
+    """A loader's `openibl_amd.jpeg.JpegBatch` (host, pinned or not) -> the decoded uint8 batch [N][H][W][3] on the
+    device, computed on the current stream (`ops.decode_jpeg`; a temporary of that stream, like the result of
+    `apply_input_resize`).  Nothing is read back: the per-image status stays on the device and is appended to
+    `pending` with the batch's file names, for `check_input_decode` when the loop has ended."""
+    from . import ops
+    from .jpeg import JpegBatch
+    if not isinstance(batch0, JpegBatch):
+        raise ValueError(f"input_decode=True decodes JpegBatch batches (a loader over Preprocessor(..., raw=True) "
+                         f"with collate_fn=openibl_amd.jpeg.collate), got {type(batch0).__name__}")
+    pixels, status = ops.decode_jpeg(batch0.to(dev, non_blocking=True), check=False)
+    pending.append((status, None if names is None else list(names)))
+    return pixels
+
+
+def check_input_decode(pending) -> None:
+    """One read-back of every status `apply_input_decode` left behind; RuntimeError lists the damaged files."""
+    if not pending:
+        return
+    from .jpeg import STATUS_TEXT
+    bad, at = [], 0
+    for status, names in pending:
+        for i, s in enumerate(status.cpu().tolist()):
+            if s:
+                who = names[i] if names is not None and i < len(names) else f"item {at + i}"
+                bad.append(f"{who} ({STATUS_TEXT[min(int(s), 4)]})")
+        at += int(status.numel())
+    del pending[:]
+    if bad:
+        raise RuntimeError(f"input_decode: {len(bad)} damaged JPEG file(s): " + ", ".join(bad))
+
+
+def _batch_names(batch):
+    return batch[1] if isinstance(batch, (tuple, list)) and len(batch) > 1 and isinstance(batch[1], (tuple, list)) \
+        else None
+
+
 def extract_descriptors(model, data_loader, vlad=True, pca=None, gpu=None, print_freq=10, rank=0,
-                        store_dtype=None, use_graphs: bool = True, input_resize=None) -> torch.Tensor:
+                        store_dtype=None, use_graphs: bool = True, input_resize=None,
+                        input_decode=None) -> torch.Tensor:
     """Descriptors of every item one rank's loader yields, in loader order, as one device matrix
     [n_local][d] (float32, or `store_dtype`).  The caller has put the model in eval mode and loaded
     `pca`.  Batches may be float32 [N][3][H][W] (normalised) or uint8 [N][H][W][3] (raw), pinned or
     not, of any mix of shapes.  `input_resize` (`input_resizer`): every batch must be uint8 and is resized on the
     device right after it got there, with PIL's bits; the loop below then sees a device-resident uint8 batch of the
-    target size — shape keys, capture, lanes and staging know nothing of the stored size."""
+    target size — shape keys, capture, lanes and staging know nothing of the stored size.  `input_decode=True`: item 0
+    of every batch is an `openibl_amd.jpeg.JpegBatch` (the files' bytes, parsed by the loader's workers) and is decoded
+    on the device in front of the resize; the statuses are read once, when the loop has ended, and a RuntimeError
+    then lists the damaged files."""
     core = unwrap_model(model)
+    decoded = []
     dev = torch.device("cuda", torch.cuda.current_device() if gpu is None else gpu)
     resize = input_resizer(input_resize)
     backbone = core.base_model.features_nhwc
@@ -618,6 +660,8 @@ def extract_descriptors(model, data_loader, vlad=True, pca=None, gpu=None, print
     with torch.no_grad():
         for i, batch in enumerate(data_loader):
             imgs = batch[0]
+            if input_decode:
+                imgs = apply_input_decode(imgs, dev, decoded, _batch_names(batch))
             if not torch.is_tensor(imgs):
                 imgs = torch.as_tensor(imgs)
             if resize is not None:
@@ -707,6 +751,7 @@ def extract_descriptors(model, data_loader, vlad=True, pca=None, gpu=None, print
                     i + 1, n_batches, t_batch, t_data))
         if last_fwd is not None:
             last_fwd.wait()
+    check_input_decode(decoded)
     if final is not None:
         return final[:row]
     if not chunks:

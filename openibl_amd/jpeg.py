@@ -1,0 +1,334 @@
+"""Host side of the device JPEG decoder (csrc/jpeg.hip, `ops.decode_jpeg`): the marker parser, the batch type and
+the DataLoader collate function.  Pure numpy; Pillow is needed only for a file the device does not decode.
+
+    parse(data)    -> Parsed: the frame, the tables, the scan's place in the file and its segments
+    probe(data)    -> (True, "") if the device decodes the file, else (False, reason)
+    collate(items) -> the loader's batch with item 0 a JpegBatch (a DataLoader `collate_fn` for
+                      `Preprocessor(..., raw=True)`): parsed in the worker, unsupported files decoded there with PIL
+    JpegBatch      packed scan bytes, records and the segment table as tensors (pinnable), the host-decoded
+                   fallbacks as pixels; `.to(device)`; `ops.decode_jpeg(batch)` gives [N][H][W][3] uint8
+
+The device decodes baseline JPEG (SOF0, 8 bit) with one scan holding all components, one component or three with the
+ids 1, 2, 3, luma factors (1,1), (2,1) or (2,2) over chroma (1,1), 8-bit quantisation tables, at most two DC and two
+AC tables (ids 0, 1), any restart interval, 8 <= W, 1 <= H, both <= 32768, no Adobe marker with a transform other
+than 1.  Everything else — progressive, CMYK / YCCK, other factors, several scans, a file that is not a JPEG, a
+narrower image — is decoded on the host and travels as pixels inside the same batch."""
+from __future__ import annotations
+
+import io
+from typing import NamedTuple, Optional
+
+import numpy as np
+import torch
+
+REC_BYTES = 1408              # JPEG_REC_BYTES of csrc/jpeg_entropy.h: int32 header[16], qt[4][64], huff[4][272]
+REC_QT, REC_HUFF, HUFF_BYTES = 64, 320, 272
+MAX_DIM, MIN_WIDTH = 32768, 8
+ST_OK, ST_BAD_CODE, ST_OVERRUN, ST_OUT_OF_BYTES, ST_BAD_RESTART = range(5)
+STATUS_TEXT = ("ok", "bad Huffman code", "coefficient index above 63", "ran out of bytes",
+               "restart marker missing or wrong")
+
+_ZIGZAG = np.array([0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20,
+                    13, 6, 7, 14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52,
+                    45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63])
+_SOF_NAMES = {0xC1: "extended sequential", 0xC2: "progressive", 0xC3: "lossless", 0xC5: "differential sequential",
+              0xC6: "differential progressive", 0xC7: "differential lossless", 0xC9: "arithmetic-coded",
+              0xCA: "arithmetic-coded progressive", 0xCB: "arithmetic-coded lossless",
+              0xCD: "arithmetic-coded differential", 0xCE: "arithmetic-coded differential progressive",
+              0xCF: "arithmetic-coded differential lossless"}
+
+
+class Parsed(NamedTuple):
+    """`reason` is "" when the device decodes the file; otherwise why it does not, and only the fields found up to
+    there are set.  record / segments / scan are what one image contributes to a JpegBatch: segments are
+    {begin, end} offsets into `scan` (the file's bytes [scan_begin, scan_stop))."""
+    reason: str
+    height: int = 0
+    width: int = 0
+    components: tuple = ()          # (id, h, v, tq) per component
+    restart_interval: int = 0
+    scan_begin: int = 0             # the first entropy-coded byte
+    scan_end: int = 0               # the FF of the marker that ends the scan (or the file's length)
+    record: Optional[np.ndarray] = None     # uint8 [REC_BYTES]; its segment fields are relative to this image
+    segments: Optional[np.ndarray] = None   # int32 [nseg][2]
+    scan: Optional[np.ndarray] = None       # uint8, the scan with the two bytes of the marker behind it
+
+    @property
+    def device(self) -> bool:
+        return not self.reason
+
+
+def _as_bytes(data) -> np.ndarray:
+    if torch.is_tensor(data):
+        data = data.numpy()
+    if isinstance(data, np.ndarray):
+        return np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
+    return np.frombuffer(bytes(data), dtype=np.uint8)
+
+
+def parse(data) -> Parsed:
+    b = _as_bytes(data)
+    n = int(b.size)
+    if n < 4 or b[0] != 0xFF or b[1] != 0xD8:
+        return Parsed("not a JPEG file")
+    qt, huff = {}, {}
+    frame = adobe = sos = None
+    dri, pos = 0, 2
+    H = W = 0
+    comps = ()
+    scan_begin = scan_end = 0
+    while pos + 4 <= n:
+        if b[pos] != 0xFF:
+            return Parsed("marker expected at byte %d" % pos)
+        m = int(b[pos + 1])
+        if m == 0xFF:                            # fill byte
+            pos += 1
+            continue
+        if m == 0xD9:
+            break
+        if m == 0x01 or 0xD0 <= m <= 0xD8:       # no length
+            pos += 2
+            continue
+        L = (int(b[pos + 2]) << 8) | int(b[pos + 3])
+        if L < 2 or pos + 2 + L > n:
+            return Parsed("truncated in front of the scan")
+        seg = b[pos + 4:pos + 2 + L]
+        if m == 0xDB and sos is None:
+            at = 0
+            while at < seg.size:
+                if seg[at] >> 4:
+                    return Parsed("16-bit quantisation table", H, W, comps)
+                if at + 65 > seg.size:
+                    return Parsed("truncated quantisation table")
+                q = np.zeros(64, np.uint8)
+                q[_ZIGZAG] = seg[at + 1:at + 65]
+                qt[int(seg[at]) & 15] = q
+                at += 65
+        elif m == 0xC4 and sos is None:
+            at = 0
+            while at < seg.size:
+                if at + 17 > seg.size:
+                    return Parsed("truncated Huffman table")
+                cnt = seg[at + 1:at + 17]
+                k = int(cnt.sum())
+                if k > 256 or at + 17 + k > seg.size or (int(seg[at]) >> 4) > 1:
+                    return Parsed("damaged Huffman table")
+                huff[(int(seg[at]) >> 4, int(seg[at]) & 15)] = (cnt.copy(), seg[at + 17:at + 17 + k].copy())
+                at += 17 + k
+        elif m == 0xC0 or m in _SOF_NAMES:
+            if frame is not None:
+                return Parsed("two frame headers")
+            if seg.size < 6 or seg.size < 6 + 3 * int(seg[5]):
+                return Parsed("truncated frame header")
+            frame = m
+            H, W = (int(seg[1]) << 8) | int(seg[2]), (int(seg[3]) << 8) | int(seg[4])
+            comps = tuple((int(seg[6 + 3 * i]), int(seg[7 + 3 * i]) >> 4, int(seg[7 + 3 * i]) & 15,
+                           int(seg[8 + 3 * i])) for i in range(int(seg[5])))
+            if m != 0xC0:
+                return Parsed(_SOF_NAMES[m], H, W, comps)
+            if seg[0] != 8:
+                return Parsed("%d-bit samples" % int(seg[0]), H, W, comps)
+        elif m == 0xDD and seg.size >= 2 and sos is None:
+            dri = (int(seg[0]) << 8) | int(seg[1])
+        elif m == 0xEE and seg.size >= 12 and bytes(seg[:5]) == b"Adobe":
+            adobe = int(seg[11])
+        elif m == 0xDA:
+            if sos is not None:
+                return Parsed("several scans", H, W, comps)
+            if frame is None:
+                return Parsed("scan in front of the frame header")
+            ns = int(seg[0]) if seg.size else 0
+            if seg.size < 4 + 2 * ns:
+                return Parsed("truncated scan header")
+            if ns != len(comps):
+                return Parsed("several scans", H, W, comps)
+            sos = ([(int(seg[1 + 2 * i]), int(seg[2 + 2 * i]) >> 4, int(seg[2 + 2 * i]) & 15) for i in range(ns)],
+                   int(seg[1 + 2 * ns]), int(seg[2 + 2 * ns]), int(seg[3 + 2 * ns]))
+            scan_begin = pos + 2 + L
+            # the scan ends at the first FF that is neither stuffed (FF 00) nor a restart marker (FF D0..D7)
+            ff = np.flatnonzero(b[scan_begin:n - 1] == 0xFF) + scan_begin
+            nxt = b[ff + 1]
+            ends = ff[(nxt != 0) & ((nxt < 0xD0) | (nxt > 0xD7))]
+            scan_end = int(ends[0]) if ends.size else n
+            pos = scan_end
+            continue
+        pos += 2 + L
+    if frame is None or sos is None:
+        return Parsed("no frame or no scan", H, W, comps)
+
+    # ---- what the device takes ---------------------------------------------------------------------------------
+    def no(reason):
+        return Parsed(reason, H, W, comps, dri, scan_begin, scan_end)
+    if not (1 <= H <= MAX_DIM and 1 <= W <= MAX_DIM):
+        return no("size %d x %d outside [1, %d]" % (H, W, MAX_DIM))
+    if W < MIN_WIDTH:
+        return no("narrower than %d pixels" % MIN_WIDTH)
+    if len(comps) not in (1, 3):
+        return no("%d components (CMYK / YCCK)" % len(comps))
+    if adobe is not None and adobe != 1:
+        return no("Adobe marker with transform %d" % adobe)
+    factors = tuple((h, v) for _, h, v, _ in comps)
+    if len(comps) == 3:
+        if tuple(c[0] for c in comps) != (1, 2, 3):
+            return no("component ids %s, not 1, 2, 3" % (tuple(c[0] for c in comps),))
+        if factors[0] not in ((1, 1), (2, 1), (2, 2)) or factors[1:] != ((1, 1), (1, 1)):
+            return no("sampling factors %s" % (factors,))
+    elif factors[0] != (1, 1):
+        return no("sampling factors %s" % (factors,))
+    scomps, ss, se, ahal = sos
+    if (ss, se, ahal) != (0, 63, 0):
+        return no("spectral selection or successive approximation in the scan header")
+    if tuple(c[0] for c in scomps) != tuple(c[0] for c in comps):
+        return no("scan components in another order")
+    for _, td, ta in scomps:
+        if td > 1 or ta > 1:
+            return no("Huffman table id above 1")
+        if (0, td) not in huff or (1, ta) not in huff:
+            return no("Huffman table missing")
+    for c in comps:
+        if c[3] > 3 or c[3] not in qt:
+            return no("quantisation table missing")
+    rst = ff[(nxt >= 0xD0) & (nxt <= 0xD7) & (ff < scan_end)]
+    if dri == 0 and rst.size:
+        return no("restart markers without a restart interval")
+
+    # ---- the record and the segments -----------------------------------------------------------------------------
+    hs, vs = factors[0] if len(comps) == 3 else (1, 1)
+    total = -(-W // (8 * hs)) * -(-H // (8 * vs))
+    want = -(-total // dri) if dri else 1
+    status = ST_OK
+    if rst.size + 1 != want or not np.array_equal(b[rst + 1], 0xD0 + (np.arange(rst.size) & 7)):
+        status = ST_BAD_RESTART
+        rst = rst[:want - 1]
+    stop = min(scan_end + 2, n)
+    segs = np.empty((rst.size + 1, 2), np.int32)
+    segs[0, 0], segs[1:, 0] = 0, rst + 2 - scan_begin
+    segs[:-1, 1], segs[-1, 1] = rst - scan_begin, scan_end - scan_begin
+    rec = np.zeros(REC_BYTES, np.uint8)
+    hdr = rec[:64].view(np.int32)
+    hdr[0], hdr[1], hdr[2] = len(comps), hs, vs
+    for i, (c, (_, td, ta)) in enumerate(zip(comps, scomps)):
+        hdr[3 + i], hdr[6 + i], hdr[9 + i] = c[3], td, ta
+    hdr[12], hdr[13], hdr[14], hdr[15] = dri, 0, segs.shape[0], status
+    for t, q in qt.items():
+        if t <= 3:
+            rec[REC_QT + 64 * t:REC_QT + 64 * t + 64] = q
+    for (tc, th), (cnt, vals) in huff.items():
+        if th <= 1:
+            at = REC_HUFF + HUFF_BYTES * (2 * tc + th)
+            rec[at:at + 16] = cnt
+            rec[at + 16:at + 16 + vals.size] = vals
+    return Parsed("", H, W, comps, dri, scan_begin, scan_end, rec, segs, b[scan_begin:stop])
+
+
+def probe(data):
+    """(True, "") if the device decodes this file, else (False, why not)."""
+    p = parse(data)
+    return p.device, p.reason
+
+
+def decode_on_host(data) -> np.ndarray:
+    """The fallback: `Image.open(...).convert('RGB')` of the file's bytes, [H][W][3] uint8."""
+    from PIL import Image      # imported on first use: only an unsupported file needs Pillow
+    with Image.open(io.BytesIO(_as_bytes(data).tobytes())) as im:
+        return np.asarray(im.convert("RGB"))
+
+
+class JpegBatch:
+    """N stored images of one size H x W on their way to `ops.decode_jpeg`.  Those the device decodes (at the batch
+    positions `dev_index`) travel as `scan` (uint8, their scans back to back), `records` (uint8 [Nd][REC_BYTES]) and
+    `segments` (int32 [S][2], offsets into `scan`); the others (`host_index`) were decoded on the host and travel as
+    `host_pixels` (uint8 [Nh][H][W][3]).  `reasons[i]` says why image i was decoded on the host ("" otherwise)."""
+
+    def __init__(self, n, height, width, scan, records, segments, max_segments, dev_index, host_index, host_pixels,
+                 reasons):
+        self.n, self.height, self.width = int(n), int(height), int(width)
+        self.scan, self.records, self.segments = scan, records, segments
+        self.max_segments = int(max_segments)
+        self.dev_index, self.host_index, self.host_pixels = dev_index, host_index, host_pixels
+        self.reasons = tuple(reasons)
+
+    _TENSORS = ("scan", "records", "segments", "dev_index", "host_index", "host_pixels")
+
+    def __len__(self):
+        return self.n
+
+    @property
+    def shape(self):
+        return (self.n, self.height, self.width, 3)
+
+    @property
+    def is_cuda(self):
+        return self.scan.is_cuda or self.host_pixels.is_cuda
+
+    @property
+    def device(self):
+        return self.scan.device
+
+    def _map(self, fn):
+        out = JpegBatch.__new__(JpegBatch)
+        out.__dict__.update(self.__dict__)
+        for name in self._TENSORS:
+            setattr(out, name, fn(getattr(self, name)))
+        return out
+
+    def to(self, device, non_blocking=False):
+        return self._map(lambda t: t.to(device, non_blocking=non_blocking))
+
+    def cuda(self, device=None, non_blocking=False):
+        dev = torch.device("cuda", torch.cuda.current_device() if device is None else device) \
+            if not isinstance(device, torch.device) else device
+        return self.to(dev, non_blocking=non_blocking)
+
+    def pin_memory(self):
+        return self._map(lambda t: t.pin_memory() if t.numel() else t)
+
+    def is_pinned(self):
+        return all(getattr(self, name).is_pinned() for name in self._TENSORS if getattr(self, name).numel())
+
+    @classmethod
+    def from_files(cls, files) -> "JpegBatch":
+        """files: the bytes of N files (bytes, numpy or 1-D uint8 tensors) of one stored size; ValueError for a mix of
+        sizes (a batch of one is always fine)."""
+        files = list(files)
+        if not files:
+            raise ValueError("JpegBatch: an empty batch")
+        scans, recs, segs, dev_idx, host_idx, host_px, reasons, sizes = [], [], [], [], [], [], [], []
+        at = nseg = max_seg = 0
+        for i, f in enumerate(files):
+            p = parse(f)
+            reasons.append(p.reason)
+            if p.device:
+                if at + p.scan.size >= 1 << 31:
+                    raise ValueError(f"JpegBatch: more than 2^31 scan bytes in one batch (at image {i})")
+                rec, sg = p.record.copy(), p.segments + np.int32(at)
+                rec[:64].view(np.int32)[13] = nseg
+                scans.append(p.scan), recs.append(rec), segs.append(sg), dev_idx.append(i)
+                at, nseg, max_seg = at + p.scan.size, nseg + sg.shape[0], max(max_seg, sg.shape[0])
+                sizes.append((p.height, p.width))
+            else:
+                px = decode_on_host(f)
+                host_idx.append(i), host_px.append(px)
+                sizes.append(px.shape[:2])
+        if len(set(sizes)) != 1:
+            raise ValueError(f"JpegBatch: images of mixed stored sizes {sorted(set(sizes))} in one batch (use a batch "
+                             f"size of 1 or a loader that groups them)")
+        H, W = sizes[0]
+        t = torch.from_numpy
+        return cls(len(files), H, W,
+                   t(np.concatenate(scans)) if scans else torch.empty(0, dtype=torch.uint8),
+                   t(np.stack(recs)) if recs else torch.empty((0, REC_BYTES), dtype=torch.uint8),
+                   t(np.concatenate(segs)) if segs else torch.empty((0, 2), dtype=torch.int32),
+                   max_seg, torch.tensor(dev_idx, dtype=torch.int64), torch.tensor(host_idx, dtype=torch.int64),
+                   t(np.stack(host_px)) if host_px else torch.empty((0, H, W, 3), dtype=torch.uint8), reasons)
+
+
+def collate(items):
+    """DataLoader `collate_fn` for a dataset whose item 0 is a file's bytes (`Preprocessor(..., raw=True)`): item 0 of
+    the batch is a JpegBatch, the other fields are collated as usual."""
+    from torch.utils.data import default_collate
+    first = items[0]
+    if torch.is_tensor(first) or isinstance(first, (bytes, bytearray, np.ndarray)):
+        return JpegBatch.from_files(items)
+    rest = default_collate([tuple(it[1:]) for it in items]) if len(first) > 1 else []
+    return [JpegBatch.from_files([it[0] for it in items])] + list(rest)

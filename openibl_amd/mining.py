@@ -138,7 +138,7 @@ def mine_from_features(q_desc, g_desc, sub_set, sampler, rerank=False, lambda_va
 
 
 def update_sampler(sampler, model, loader, query, gallery, sub_set, rerank=False, vlad=True, gpu=None,
-                   sync_gather=False, lambda_value=0.1, trunk_cache=None, input_resize=None):
+                   sync_gather=False, lambda_value=0.1, trunk_cache=None, input_resize=None, input_decode=None):
     """The `update_sampler` of examples/netvlad_img.py and netvlad_img_sfrs.py with the descriptors, the
     distances and the mining on the device: extract over sorted(set(query) | set(gallery)) (`loader`'s
     dataset, as in the scripts), look the rows up by file name, mine this round's anchors, load the sampler.
@@ -147,7 +147,9 @@ def update_sampler(sampler, model, loader, query, gallery, sub_set, rerank=False
     descriptors then come from its stored pool4 maps (conv5 and the head with the live parameters, the same bits),
     `loader` is not iterated and no image is decoded; everything behind the extraction is unchanged.
     input_resize: as in `extract_features` — `loader` delivers raw uint8 batches at their stored size, resized on the
-    device (a trunk cache was filled behind the same resize: `TrunkCache.fill(..., input_resize=...)`)."""
+    device (a trunk cache was filled behind the same resize: `TrunkCache.fill(..., input_resize=...)`).
+    input_decode: as in `extract_features` — `loader` delivers the files' bytes as JpegBatch batches, decoded on the
+    device in front of the resize."""
     from .evaluators import _extract_local, _rank_world
     rank, world = _rank_world()
     if world != 1:
@@ -165,7 +167,8 @@ def update_sampler(sampler, model, loader, query, gallery, sub_set, rerank=False
         trunk_cache.check(model, len(dataset))
         feats = trunk_cache.descriptors(model, vlad)
     else:
-        feats = _extract_local(model, loader, vlad, None, gpu, 10, rank, input_resize=input_resize)[:len(dataset)]
+        feats = _extract_local(model, loader, vlad, None, gpu, 10, rank, input_resize=input_resize,
+                               input_decode=input_decode)[:len(dataset)]
     where = {f: i for i, (f, *_) in enumerate(dataset)}
     q_feat = feats[torch.as_tensor([where[f] for f, *_ in query], device=feats.device)]
     g_feat = feats[torch.as_tensor([where[f] for f, *_ in gallery], device=feats.device)]

@@ -2085,3 +2085,50 @@ def resize_u8(u8: torch.Tensor, size, out: str = "uint8", mean=REF_MEAN, std=REF
     _lib.check(lib.oibl_resize_u8(_ptr(u8), N, H, W, H2, W2, JITTER_OUT[out], m3, s3, _ptr(res), _ptr(ws),
                                   ws.numel(), _stream(dev)), "resize_u8")
     return res
+
+
+# ---------------------------------------------------------------------------------------------
+def decode_jpeg(batch, check: bool = True):
+    """Decode a `openibl_amd.jpeg.JpegBatch` on the device (oibl_jpeg_decode): [N][H][W][3] uint8, the bytes of
+    `np.asarray(Image.open(f).convert('RGB'))` for every file.  The files the device does not decode (progressive,
+    CMYK, not a JPEG, ...) were decoded on the host when the batch was built and are copied into their places.
+    check=True reads the per-image status back (one host sync) and raises ValueError naming the damaged images;
+    check=False returns (pixels, status) without a sync: status int32 [N], 0 ok (`jpeg.STATUS_TEXT`), 0 for the
+    host-decoded images."""
+    from . import jpeg as _jpeg
+    if not isinstance(batch, _jpeg.JpegBatch):
+        raise ValueError(f"decode_jpeg expects a JpegBatch (openibl_amd.jpeg.collate), got {type(batch).__name__}")
+    dev = _need_cuda(batch.scan, batch.records, batch.segments, batch.host_pixels, batch.dev_index,
+                     batch.host_index)
+    N, H, W = batch.n, batch.height, batch.width
+    nd, nh = int(batch.records.shape[0]), int(batch.host_pixels.shape[0])
+    if nd + nh != N or batch.records.shape[1:] != (_jpeg.REC_BYTES,) or batch.host_pixels.shape[1:] != (H, W, 3):
+        raise ValueError(f"decode_jpeg: inconsistent batch: {nd} records + {nh} host images for N = {N}")
+    status = torch.zeros(N, dtype=torch.int32, device=dev)
+    pixels = None
+    if nd:
+        if not (_jpeg.MIN_WIDTH <= W <= _jpeg.MAX_DIM and 1 <= H <= _jpeg.MAX_DIM and nd <= 65535):
+            raise ValueError(f"decode_jpeg: {nd} images of {H} x {W}: at most 65535 of at least "
+                             f"{_jpeg.MIN_WIDTH} and at most {_jpeg.MAX_DIM} pixels per side")
+        lib = _lib.load()
+        S = int(batch.segments.shape[0])
+        pixels = torch.empty((nd, H, W, 3), dtype=torch.uint8, device=dev)
+        st = status if nh == 0 else torch.empty(nd, dtype=torch.int32, device=dev)
+        ws = workspace(lib.oibl_jpeg_decode_workspace_bytes(nd, H, W, S), dev, slot="jpeg_decode")
+        _lib.check(lib.oibl_jpeg_decode(_ptr(batch.scan), batch.scan.numel(), _ptr(batch.records),
+                                        _ptr(batch.segments), S, batch.max_segments, nd, H, W, _ptr(pixels),
+                                        _ptr(st), _ptr(ws), ws.numel(), _stream(dev)), "jpeg_decode")
+    if nh:
+        out = torch.empty((N, H, W, 3), dtype=torch.uint8, device=dev)
+        out[batch.host_index] = batch.host_pixels
+        if nd:
+            out[batch.dev_index] = pixels
+            status[batch.dev_index] = st
+        pixels = out
+    if not check:
+        return pixels, status
+    bad = status.cpu().numpy()
+    if bad.any():
+        raise ValueError("decode_jpeg: damaged JPEG streams: " + ", ".join(
+            f"image {i} ({_jpeg.STATUS_TEXT[min(int(s), 4)]})" for i, s in enumerate(bad) if s))
+    return pixels

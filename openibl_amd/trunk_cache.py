@@ -85,14 +85,17 @@ class TrunkCache:
     # ---- fill -----------------------------------------------------------------------------------
     @classmethod
     def fill(cls, model, loader, dataset, gpu=None, max_bytes: Optional[int] = None,
-             input_resize=None) -> "TrunkCache":
+             input_resize=None, input_decode=None) -> "TrunkCache":
         """Run `loader` (the extraction loader over `dataset`, fp32 [N][3][H][W] or uint8 [N][H][W][3] batches in
         dataset order) once, eagerly, under no_grad in eval mode, and keep every batch's stored pool4 activation.
         max_bytes: refuse (ValueError) a cache above it; default a quarter of the device's free memory now.
-        input_resize: as in `extract_features` — the loader's raw uint8 batches are resized on the device first."""
+        input_resize: as in `extract_features` — the loader's raw uint8 batches are resized on the device first.
+        input_decode: as in `extract_features` — the loader's JpegBatch batches are decoded on the device in front of
+        that; RuntimeError lists the damaged files when the loader has ended."""
         from .evaluators import _rank_world
-        from .extract import apply_input_resize, input_resizer
+        from .extract import _batch_names, apply_input_decode, apply_input_resize, check_input_decode, input_resizer
         resize = input_resizer(input_resize)
+        decoded = []
         rank, world = _rank_world()
         if world != 1:
             raise RuntimeError(
@@ -118,6 +121,8 @@ class TrunkCache:
         with torch.no_grad():
             for batch in loader:
                 imgs = batch[0]
+                if input_decode:
+                    imgs = apply_input_decode(imgs, dev, decoded, _batch_names(batch))
                 if not torch.is_tensor(imgs):
                     imgs = torch.as_tensor(imgs)
                 if resize is not None:
@@ -152,6 +157,7 @@ class TrunkCache:
                                      "dataset announce")
                 batches.append(cache._fill_batch(base, x, row))
                 row += n
+        check_input_decode(decoded)
         if lines is None or row < n_items:
             raise ValueError(f"TrunkCache.fill: the loader yielded {row} images, the dataset holds {n_items}")
         torch.cuda.current_stream(dev).synchronize()
