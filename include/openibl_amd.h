@@ -822,6 +822,25 @@ int oibl_jpeg_decode(const uint8_t* scan_bytes, size_t scan_len, const void* rec
                      int max_segments, int N, int H, int W, uint8_t* out_nhwc, int32_t* status, void* ws,
                      size_t ws_bytes, void* stream);
 
+/* The same decoder with many lanes inside one segment, for scans without restart markers, where oibl_jpeg_decode has
+ * one lane per image (csrc/jpeg_chunked.hip and csrc/jpeg_chunked.h state the method: self-synchronising Huffman
+ * decoding).  Arguments, record, segment table, output and status are those of oibl_jpeg_decode, and so are the bits.
+ * Every segment is cut into chunks of chunk_bytes raw bytes (4 <= chunk_bytes <= 65536); one workgroup serves a
+ * segment with a lane per chunk, at most 1024 — the last lane takes what is left.  The lanes decode their chunks from
+ * a guessed state without writing, exchange exit states through LDS until no lane's entry changes (at most as many
+ * rounds as lanes, separated by workgroup barriers: no waiting on another workgroup, no spinning, no atomics), take
+ * their first block and DC predictors from a prefix over the chunks and decode once more, strictly, into the zeroed
+ * coefficients.  The one difference from oibl_jpeg_decode: behind the first damaged block of a damaged segment the
+ * coefficients may hold other bounded garbage than there; in front of it, and in the status, there is none.
+ * One memset and three launches, stream-ordered and capturable; validation as for oibl_jpeg_decode, before anything
+ * is launched.  Workspace: int16 coef[N][3][Bh][Bw][64], int32 segment status [S], int32 settle rounds [S] (for
+ * measurements), uint8 planes[N][3][Bh * 8][Bw * 8], each aligned to 256 bytes;
+ * oibl_jpeg_decode_chunked_workspace_bytes returns 0 for what the call rejects. */
+size_t oibl_jpeg_decode_chunked_workspace_bytes(int N, int H, int W, int S, int chunk_bytes);
+int oibl_jpeg_decode_chunked(const uint8_t* scan_bytes, size_t scan_len, const void* records, const int32_t* segments,
+                             int S, int max_segments, int N, int H, int W, int chunk_bytes, uint8_t* out_nhwc,
+                             int32_t* status, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- recall counting ---------------------------------------------------------------- *
  * Replaces the per-query Python loop of evaluate_all and spatial_nms
  * (ibl/evaluators.py:132-140, 149-160).  For every query, the rank (0-based, inside the

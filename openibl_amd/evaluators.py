@@ -90,6 +90,7 @@ def _extract_local(model, data_loader, vlad, pca, gpu, print_freq, rank, scales=
     if pca is not None:
         pca.load(gpu=gpu)
     from . import extract
+    from .jpeg import scan_route
     if FAST_EXTRACTION and scales is None and extract.fast_path_supported(model):
         return extract.extract_descriptors(model, data_loader, vlad=vlad, pca=pca, gpu=gpu,
                                            print_freq=print_freq, rank=rank, store_dtype=store_dtype,
@@ -104,7 +105,8 @@ def _extract_local(model, data_loader, vlad, pca, gpu, print_freq, rank, scales=
         for i, batch in enumerate(data_loader):
             imgs = batch[0]
             if input_decode:
-                imgs = extract.apply_input_decode(imgs, _device(gpu), decoded, extract._batch_names(batch))
+                imgs = extract.apply_input_decode(imgs, _device(gpu), decoded, extract._batch_names(batch),
+                                                  scan=scan_route(input_decode))
             if resize is not None:
                 imgs = extract.apply_input_resize(resize, torch.as_tensor(imgs), _device(gpu))
             data_t.update(time.time() - end)
@@ -167,7 +169,9 @@ def extract_features(model, data_loader, dataset, print_freq=10, vlad=True, pca=
     `openibl_amd.jpeg.JpegBatch` (files of one stored size per batch).  Every batch is decoded on the device right
     after it got there (`ops.decode_jpeg`: baseline JPEG with Pillow's bits; a file the device does not decode was
     decoded by the worker and travels as pixels), in front of `input_resize`.  The statuses are read once, when the
-    loop has ended: RuntimeError lists the damaged files.  A tensor batch raises ValueError.
+    loop has ended: RuntimeError lists the damaged files.  A tensor batch raises ValueError.  "serial" or "chunked"
+    in place of True names the route of `ops.decode_jpeg` (True is "auto": chunked for long segments, that is for
+    files without restart markers).
 
     Each rank extracts the slice its DistributedSliceSampler yields; slices are gathered
     rank-major and truncated to len(dataset) (the wrap-around padding of the last slices).

@@ -586,17 +586,18 @@ def apply_input_resize(resize, imgs: torch.Tensor, dev) -> torch.Tensor:
     return resize(imgs.contiguous().to(dev, non_blocking=True))
 
 
-def apply_input_decode(batch0, dev, pending, names=None) -> torch.Tensor:
+def apply_input_decode(batch0, dev, pending, names=None, scan="auto") -> torch.Tensor:
     """A loader's `openibl_amd.jpeg.JpegBatch` (host, pinned or not) -> the decoded uint8 batch [N][H][W][3] on the
     device, computed on the current stream (`ops.decode_jpeg`; a temporary of that stream, like the result of
     `apply_input_resize`).  Nothing is read back: the per-image status stays on the device and is appended to
-    `pending` with the batch's file names, for `check_input_decode` when the loop has ended."""
+    `pending` with the batch's file names, for `check_input_decode` when the loop has ended.  scan: the route of
+    `ops.decode_jpeg` ("auto", "serial", "chunked")."""
     from . import ops
     from .jpeg import JpegBatch
     if not isinstance(batch0, JpegBatch):
         raise ValueError(f"input_decode=True decodes JpegBatch batches (a loader over Preprocessor(..., raw=True) "
                          f"with collate_fn=openibl_amd.jpeg.collate), got {type(batch0).__name__}")
-    pixels, status = ops.decode_jpeg(batch0.to(dev, non_blocking=True), check=False)
+    pixels, status = ops.decode_jpeg(batch0.to(dev, non_blocking=True), check=False, scan=scan)
     pending.append((status, None if names is None else list(names)))
     return pixels
 
@@ -634,7 +635,9 @@ def extract_descriptors(model, data_loader, vlad=True, pca=None, gpu=None, print
     target size — shape keys, capture, lanes and staging know nothing of the stored size.  `input_decode=True`: item 0
     of every batch is an `openibl_amd.jpeg.JpegBatch` (the files' bytes, parsed by the loader's workers) and is decoded
     on the device in front of the resize; the statuses are read once, when the loop has ended, and a RuntimeError
-    then lists the damaged files."""
+    then lists the damaged files.  `input_decode` may also name the route of `ops.decode_jpeg` ("serial", "chunked";
+    True is "auto")."""
+    from .jpeg import scan_route
     core = unwrap_model(model)
     decoded = []
     dev = torch.device("cuda", torch.cuda.current_device() if gpu is None else gpu)
@@ -661,7 +664,7 @@ def extract_descriptors(model, data_loader, vlad=True, pca=None, gpu=None, print
         for i, batch in enumerate(data_loader):
             imgs = batch[0]
             if input_decode:
-                imgs = apply_input_decode(imgs, dev, decoded, _batch_names(batch))
+                imgs = apply_input_decode(imgs, dev, decoded, _batch_names(batch), scan=scan_route(input_decode))
             if not torch.is_tensor(imgs):
                 imgs = torch.as_tensor(imgs)
             if resize is not None:

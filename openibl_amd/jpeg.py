@@ -27,6 +27,17 @@ MAX_DIM, MIN_WIDTH = 32768, 8
 ST_OK, ST_BAD_CODE, ST_OVERRUN, ST_OUT_OF_BYTES, ST_BAD_RESTART = range(5)
 STATUS_TEXT = ("ok", "bad Huffman code", "coefficient index above 63", "ran out of bytes",
                "restart marker missing or wrong")
+# The chunked route of `ops.decode_jpeg` (csrc/jpeg_chunked.hip): many lanes inside one segment.  scan="auto" takes it
+# when the batch's longest segment has at least CHUNKED_MIN_BYTES bytes; a lane's chunk has CHUNK_BYTES raw bytes, more
+# where a segment would otherwise have more than MAX_CHUNK_LANES chunks.  Both are set from one run on an MI355X
+# (profiles/jpeg_chunked_bench.txt, files of 480 x 640): wherever the chunked route wins, 64-byte chunks were as fast as
+# 128-byte ones or faster (32 files: 3.23 against 3.25 ms, 1024 files: 14.2 against 15.0 ms) and faster than 256 and
+# 512; of the segment sizes measured the chunked route loses to the serial one at 1.5 kB (one restart per MCU row)
+# and wins from 6.0 kB on (one per four rows; the longest segment of those files has 6031 bytes).
+CHUNK_BYTES = 64
+CHUNKED_MIN_BYTES = 6000
+MAX_CHUNK_LANES = 1024
+SCAN_ROUTES = ("auto", "serial", "chunked")
 
 _ZIGZAG = np.array([0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20,
                     13, 6, 7, 14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52,
@@ -238,13 +249,15 @@ class JpegBatch:
     """N stored images of one size H x W on their way to `ops.decode_jpeg`.  Those the device decodes (at the batch
     positions `dev_index`) travel as `scan` (uint8, their scans back to back), `records` (uint8 [Nd][REC_BYTES]) and
     `segments` (int32 [S][2], offsets into `scan`); the others (`host_index`) were decoded on the host and travel as
-    `host_pixels` (uint8 [Nh][H][W][3]).  `reasons[i]` says why image i was decoded on the host ("" otherwise)."""
+    `host_pixels` (uint8 [Nh][H][W][3]).  `reasons[i]` says why image i was decoded on the host ("" otherwise).
+    `max_segment_bytes`: the longest segment, which chooses the route of `ops.decode_jpeg(scan="auto")`."""
 
     def __init__(self, n, height, width, scan, records, segments, max_segments, dev_index, host_index, host_pixels,
-                 reasons):
+                 reasons, max_segment_bytes=0):
         self.n, self.height, self.width = int(n), int(height), int(width)
         self.scan, self.records, self.segments = scan, records, segments
         self.max_segments = int(max_segments)
+        self.max_segment_bytes = int(max_segment_bytes)
         self.dev_index, self.host_index, self.host_pixels = dev_index, host_index, host_pixels
         self.reasons = tuple(reasons)
 
@@ -294,7 +307,7 @@ class JpegBatch:
         if not files:
             raise ValueError("JpegBatch: an empty batch")
         scans, recs, segs, dev_idx, host_idx, host_px, reasons, sizes = [], [], [], [], [], [], [], []
-        at = nseg = max_seg = 0
+        at = nseg = max_seg = max_bytes = 0
         for i, f in enumerate(files):
             p = parse(f)
             reasons.append(p.reason)
@@ -305,6 +318,7 @@ class JpegBatch:
                 rec[:64].view(np.int32)[13] = nseg
                 scans.append(p.scan), recs.append(rec), segs.append(sg), dev_idx.append(i)
                 at, nseg, max_seg = at + p.scan.size, nseg + sg.shape[0], max(max_seg, sg.shape[0])
+                max_bytes = max(max_bytes, int((sg[:, 1] - sg[:, 0]).max()))
                 sizes.append((p.height, p.width))
             else:
                 px = decode_on_host(f)
@@ -320,7 +334,18 @@ class JpegBatch:
                    t(np.stack(recs)) if recs else torch.empty((0, REC_BYTES), dtype=torch.uint8),
                    t(np.concatenate(segs)) if segs else torch.empty((0, 2), dtype=torch.int32),
                    max_seg, torch.tensor(dev_idx, dtype=torch.int64), torch.tensor(host_idx, dtype=torch.int64),
-                   t(np.stack(host_px)) if host_px else torch.empty((0, H, W, 3), dtype=torch.uint8), reasons)
+                   t(np.stack(host_px)) if host_px else torch.empty((0, H, W, 3), dtype=torch.uint8), reasons,
+                   max_bytes)
+
+
+def scan_route(input_decode) -> str:
+    """The `scan` of `ops.decode_jpeg` an `input_decode` argument asks for: a route's name is itself, anything else
+    that is true is "auto"."""
+    if not isinstance(input_decode, str):
+        return "auto"
+    if input_decode in SCAN_ROUTES:
+        return input_decode
+    raise ValueError(f"input_decode must be True or one of {SCAN_ROUTES}, not {input_decode!r}")
 
 
 def collate(items):

@@ -2088,16 +2088,35 @@ def resize_u8(u8: torch.Tensor, size, out: str = "uint8", mean=REF_MEAN, std=REF
 
 
 # ---------------------------------------------------------------------------------------------
-def decode_jpeg(batch, check: bool = True):
-    """Decode a `openibl_amd.jpeg.JpegBatch` on the device (oibl_jpeg_decode): [N][H][W][3] uint8, the bytes of
-    `np.asarray(Image.open(f).convert('RGB'))` for every file.  The files the device does not decode (progressive,
-    CMYK, not a JPEG, ...) were decoded on the host when the batch was built and are copied into their places.
+def _align256(v: int) -> int:
+    return (v + 255) // 256 * 256
+
+
+last_jpeg_route = None     # "serial" or "chunked": the route the last `decode_jpeg` that launched something took
+last_jpeg_rounds = None    # chunked: int32 [S] on the device, the settle rounds of every segment (a view of the
+                           # workspace, valid until the next call)
+
+
+def decode_jpeg(batch, check: bool = True, scan: str = "auto", chunk_bytes=None):
+    """Decode a `openibl_amd.jpeg.JpegBatch` on the device (oibl_jpeg_decode / oibl_jpeg_decode_chunked):
+    [N][H][W][3] uint8, the bytes of `np.asarray(Image.open(f).convert('RGB'))` for every file.  The files the device
+    does not decode (progressive, CMYK, not a JPEG, ...) were decoded on the host when the batch was built and are
+    copied into their places.
+    scan: "serial" gives every segment (a restart interval, or a whole scan) one lane; "chunked" cuts every segment
+    into chunks of `chunk_bytes` raw bytes (default: `jpeg.CHUNK_BYTES`, more where the longest segment would have
+    more than 1024 chunks) with a lane each — the same bits, for files without restart markers; "auto" takes the
+    chunked route when the batch's longest segment has at least `jpeg.CHUNKED_MIN_BYTES` bytes.
     check=True reads the per-image status back (one host sync) and raises ValueError naming the damaged images;
     check=False returns (pixels, status) without a sync: status int32 [N], 0 ok (`jpeg.STATUS_TEXT`), 0 for the
     host-decoded images."""
+    global last_jpeg_route, last_jpeg_rounds
     from . import jpeg as _jpeg
     if not isinstance(batch, _jpeg.JpegBatch):
         raise ValueError(f"decode_jpeg expects a JpegBatch (openibl_amd.jpeg.collate), got {type(batch).__name__}")
+    if scan not in _jpeg.SCAN_ROUTES:
+        raise ValueError(f"decode_jpeg: scan must be one of {_jpeg.SCAN_ROUTES}, not {scan!r}")
+    if chunk_bytes is not None and not 4 <= int(chunk_bytes) <= 65536:
+        raise ValueError(f"decode_jpeg: chunk_bytes {chunk_bytes} must be in [4, 65536]")
     dev = _need_cuda(batch.scan, batch.records, batch.segments, batch.host_pixels, batch.dev_index,
                      batch.host_index)
     N, H, W = batch.n, batch.height, batch.width
@@ -2114,10 +2133,27 @@ def decode_jpeg(batch, check: bool = True):
         S = int(batch.segments.shape[0])
         pixels = torch.empty((nd, H, W, 3), dtype=torch.uint8, device=dev)
         st = status if nh == 0 else torch.empty(nd, dtype=torch.int32, device=dev)
-        ws = workspace(lib.oibl_jpeg_decode_workspace_bytes(nd, H, W, S), dev, slot="jpeg_decode")
-        _lib.check(lib.oibl_jpeg_decode(_ptr(batch.scan), batch.scan.numel(), _ptr(batch.records),
-                                        _ptr(batch.segments), S, batch.max_segments, nd, H, W, _ptr(pixels),
-                                        _ptr(st), _ptr(ws), ws.numel(), _stream(dev)), "jpeg_decode")
+        if scan == "auto":
+            scan = "chunked" if batch.max_segment_bytes >= _jpeg.CHUNKED_MIN_BYTES else "serial"
+        if scan == "chunked":
+            cb = int(chunk_bytes) if chunk_bytes is not None else \
+                min(65536, max(_jpeg.CHUNK_BYTES, -(-batch.max_segment_bytes // _jpeg.MAX_CHUNK_LANES)))
+            need = lib.oibl_jpeg_decode_chunked_workspace_bytes(nd, H, W, S, cb)
+            ws = workspace(need, dev, slot="jpeg_decode")
+            _lib.check(lib.oibl_jpeg_decode_chunked(_ptr(batch.scan), batch.scan.numel(), _ptr(batch.records),
+                                                    _ptr(batch.segments), S, batch.max_segments, nd, H, W, cb,
+                                                    _ptr(pixels), _ptr(st), _ptr(ws), ws.numel(), _stream(dev)),
+                       "jpeg_decode_chunked")
+            # the workspace: int16 coef[nd][3][Bh][Bw][64], int32 segment status [S], int32 rounds [S], the planes
+            at = _align256(nd * 3 * (2 * ((H + 15) // 16)) * (2 * ((W + 15) // 16)) * 64 * 2) + _align256(4 * S)
+            last_jpeg_rounds = ws[at:at + 4 * S].view(torch.int32)
+        else:
+            ws = workspace(lib.oibl_jpeg_decode_workspace_bytes(nd, H, W, S), dev, slot="jpeg_decode")
+            _lib.check(lib.oibl_jpeg_decode(_ptr(batch.scan), batch.scan.numel(), _ptr(batch.records),
+                                            _ptr(batch.segments), S, batch.max_segments, nd, H, W, _ptr(pixels),
+                                            _ptr(st), _ptr(ws), ws.numel(), _stream(dev)), "jpeg_decode")
+            last_jpeg_rounds = None
+        last_jpeg_route = scan
     if nh:
         out = torch.empty((N, H, W, 3), dtype=torch.uint8, device=dev)
         out[batch.host_index] = batch.host_pixels

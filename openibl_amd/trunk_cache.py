@@ -94,6 +94,7 @@ class TrunkCache:
         that; RuntimeError lists the damaged files when the loader has ended."""
         from .evaluators import _rank_world
         from .extract import _batch_names, apply_input_decode, apply_input_resize, check_input_decode, input_resizer
+        from .jpeg import scan_route
         resize = input_resizer(input_resize)
         decoded = []
         rank, world = _rank_world()
@@ -122,7 +123,7 @@ class TrunkCache:
             for batch in loader:
                 imgs = batch[0]
                 if input_decode:
-                    imgs = apply_input_decode(imgs, dev, decoded, _batch_names(batch))
+                    imgs = apply_input_decode(imgs, dev, decoded, _batch_names(batch), scan=scan_route(input_decode))
                 if not torch.is_tensor(imgs):
                     imgs = torch.as_tensor(imgs)
                 if resize is not None:
