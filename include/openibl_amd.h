@@ -841,6 +841,69 @@ int oibl_jpeg_decode_chunked(const uint8_t* scan_bytes, size_t scan_len, const v
                              int S, int max_segments, int N, int H, int W, int chunk_bytes, uint8_t* out_nhwc,
                              int32_t* status, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- JPEG batches of mixed stored sizes -------------------------------------------------------- *
+ * The decoder and the resize above for a batch whose images have sizes of their own (a folder that mixes portrait and
+ * landscape, or several camera resolutions): all segments of all images decode in ONE entropy launch into a PACKED
+ * pixel buffer — image n a contiguous [H_n][W_n][3] uint8 block at its byte offset — and ONE resize launch reads the
+ * packed buffer into the dense batch [N][H2][W2][3] the model takes.  The arithmetic, the record, the segment table,
+ * the statuses and the bits are those of oibl_jpeg_decode / oibl_jpeg_decode_chunked / oibl_resize_u8 (the same
+ * kernel text: csrc/jpeg_stages.h, resize_tile of csrc/resize.hip); an image's result does not depend on its batch
+ * mates or its position.  The uniform entry points stay what a batch of one size takes.
+ *
+ * oibl_jpeg_mixed_layout (host only, nothing is launched or copied): sizes_host [N][2] int32 = {H, W} ->
+ *   geom_host [N][8] int32, the per-image geometry table: 0 H; 1 W; 2 the image's base in the int16 coefficients, in
+ *             blocks of 64 coefficients; 3 its base in the uint8 sample planes, in units of 64 bytes (the same number:
+ *             the images lie back to back in both, each as [3][Bh][Bw] blocks with Bw = 2 ceil(W / 16),
+ *             Bh = 2 ceil(H / 16), the uniform decoder's 9 bytes per MCU-padded pixel); 4, 5 its byte offset in the
+ *             packed pixels, low 32 bits and high bits (every image starts on a multiple of 64 bytes); 6, 7 zero.
+ *   totals_host [6] size_t: 0 coefficient bytes; 1 sample-plane bytes; 2 packed pixel bytes (the end of the last
+ *             image); 3 the largest Bw * Bh; 4 the largest H; 5 the largest W.
+ *   1 <= N <= 65535, every side in [1, 32768], fewer than 2^31 coefficient blocks and fewer than 2^40 packed pixel
+ *   bytes; otherwise OIBL_E_INVALID with a message that names the image.  The caller copies the table to the device
+ *   with the batch's other tensors; a caller that decodes only some of the images (the others were decoded on the
+ *   host and copied into their slots of the packed buffer) lays those out on their own for entries 2 and 3 and keeps
+ *   entries 4 and 5 of the whole batch's layout.
+ *
+ * oibl_jpeg_decode_mixed: scan_bytes, scan_len, records, segments, S, max_segments, N, status as for oibl_jpeg_decode
+ *   (N images with a record each, 8 <= W_n).
+ *   geom_dev [N][8] int32 (device, 4-byte aligned), totals_host [6] (host) as above.
+ *   chunk_bytes   0: the serial route, a lane per segment; 4..65536: the chunked route, a workgroup per segment.
+ *   out_packed    uint8 [totals_host[2]] (device): only the bytes of the N images are written.
+ *   status [N]    as for oibl_jpeg_decode, and 5: the image's row of the geometry table is inconsistent — a side
+ *                 outside its range or beyond totals_host[4] / [5], or an extent that passes the end of the
+ *                 coefficients, the planes or the packed pixels as totals_host gives them.  Such an image is skipped
+ *                 by every stage.  Every entry of the table is forced into its range on the device and every extent
+ *                 is checked there against the call's totals: no read or write depends on the table being right.
+ *   One memset and three launches, stream-ordered and capturable; the grids of the IDCT and colour stages are sized by
+ *   totals_host[3..5], and a workgroup outside its image leaves at once.  OIBL_E_INVALID before anything is launched
+ *   for a null pointer, N or S outside 1 <= N <= 65535, N <= S <= 2^28, totals that no layout has, chunk_bytes,
+ *   scan_len, max_segments or a misaligned pointer; a short workspace is OIBL_E_WORKSPACE.
+ *   Workspace: int16 coef [totals_host[0] bytes], int32 segment status [S], int32 settle rounds [S], uint8 planes
+ *   [totals_host[1] bytes], each aligned to 256 bytes; oibl_jpeg_decode_mixed_workspace_bytes returns 0 for what the
+ *   call rejects.
+ *
+ * oibl_resize_u8_mixed: packed [packed_bytes] uint8 (device), geom_dev [N][8] (entries 0, 1, 4, 5 are read),
+ *   sizes_host [N][2] int32 = {H, W} (host: it sizes the tables, the LDS and checks the limits), H2, W2, out_kind,
+ *   mean3_host, std3_host, out as for oibl_resize_u8: out [N][H2][W2][3] uint8 or [N][3][H2][W2] fp32.
+ *   Two launches: one builds every image's two tables into the workspace, with rows of the batch's largest ksize per
+ *   axis; one runs both passes for every tile of every image, its LDS sized by the batch's largest need.  The limits
+ *   are those of oibl_resize_u8 per image (H_n <= 16 H2, W_n <= 16 W2, every size <= 32768, N <= 65535) and
+ *   1 <= packed_bytes < 2^40; OIBL_E_INVALID names the image.  On the device H_n, W_n are forced into [1, the largest
+ *   of sizes_host] and the extent is checked against packed_bytes; an image whose row fails that check reads nothing
+ *   and its output is that of zero bytes.
+ *   Workspace: int32 bounds_h [N][W2][2], coeff_h [N][W2][ksh], bounds_v [N][H2][2], coeff_v [N][H2][ksv], each
+ *   aligned to 256 bytes; oibl_resize_u8_mixed_workspace_bytes returns 0 for what the call rejects. */
+int oibl_jpeg_mixed_layout(const int32_t* sizes_host, int N, int32_t* geom_host, size_t* totals_host);
+size_t oibl_jpeg_decode_mixed_workspace_bytes(const size_t* totals_host, int N, int S);
+int oibl_jpeg_decode_mixed(const uint8_t* scan_bytes, size_t scan_len, const void* records, const int32_t* segments,
+                           int S, int max_segments, int N, const int32_t* geom_dev, const size_t* totals_host,
+                           int chunk_bytes, uint8_t* out_packed, int32_t* status, void* ws, size_t ws_bytes,
+                           void* stream);
+size_t oibl_resize_u8_mixed_workspace_bytes(const int32_t* sizes_host, int N, int H2, int W2);
+int oibl_resize_u8_mixed(const uint8_t* packed, size_t packed_bytes, const int32_t* geom_dev,
+                         const int32_t* sizes_host, int N, int H2, int W2, int out_kind, const float* mean3_host,
+                         const float* std3_host, void* out, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- recall counting ---------------------------------------------------------------- *
  * Replaces the per-query Python loop of evaluate_all and spatial_nms
  * (ibl/evaluators.py:132-140, 149-160).  For every query, the rank (0-based, inside the

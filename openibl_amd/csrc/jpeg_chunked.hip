@@ -1,7 +1,8 @@
 // The chunked route of the device JPEG decoder: the entropy stage of csrc/jpeg.hip with many lanes per segment, for
 // scans without restart markers (one lane per image there).  A segment — a restart interval, or a whole scan — is cut
 // into chunks of `chunk_bytes` raw bytes; ONE workgroup serves it, a lane per chunk, at most 1024 (the last lane takes
-// what is left).  The state machine is the shared text of jpeg_chunked.h; this file is its schedule:
+// what is left).  The state machine is the shared text of jpeg_chunked.h; its schedule is jpeg_chunked_segment of
+// jpeg_stages.h (csrc/jpeg_mixed.hip runs the same schedule on images of mixed sizes):
 //
 //   speculate   every lane but the last decodes its chunk from the guess (first bit, block 0 of an MCU, DC next),
 //               without writing, and keeps its exit state and what the chunk owns;
@@ -20,12 +21,11 @@
 // came from the tolerant speculation may leave other (bounded) garbage than the serial route leaves zeros.
 #include "common.h"
 
-#include "jpeg_chunked.h"
 #include "jpeg_kernels.h"
+#include "jpeg_stages.h"
 
 namespace oibl {
 
-constexpr int JSCAN_MAX_LANES = 1024;
 constexpr int JSCAN_MAX_DIM = 32768;
 
 __constant__ uint8_t c_jscan_zigzag[64] = {JPEG_ZIGZAG_LIST};
@@ -38,75 +38,16 @@ __global__ __launch_bounds__(JSCAN_MAX_LANES) void jscan_chunk_kernel(const uint
                                                                       int32_t* seg_rounds) {
   __shared__ JpegHuff s_huff[4];
   __shared__ uint8_t s_zz[64];
-  __shared__ uint32_t s_a[JSCAN_MAX_LANES], s_b[JSCAN_MAX_LANES], s_c[JSCAN_MAX_LANES], s_d[JSCAN_MAX_LANES];
-  const int tid = threadIdx.x, T = blockDim.x, k = blockIdx.x, n = blockIdx.y;
+  const int tid = threadIdx.x, k = blockIdx.x, n = blockIdx.y;
   const uint8_t* rec = records + (size_t)n * JPEG_REC_BYTES;
   const JpegGeom g = jpeg_geom(reinterpret_cast<const int32_t*>(rec), H, W);
   if (k >= g.nseg || g.seg_first > S - 1 - k) return;   // the whole workgroup
   if (tid < 4) jpeg_huff_build(&s_huff[tid], rec + JPEG_REC_HUFF + tid * JPEG_HUFF_BYTES);
   if (tid < 64) s_zz[tid] = c_jscan_zigzag[tid];
   __syncthreads();
-  const int sidx = g.seg_first + k;
-  const JpegChunkGeom q = jpeg_chunk_geom(g);
-  const JpegChunkSeg sg = jpeg_chunk_segment(g, q, k, segs[2 * sidx], segs[2 * sidx + 1], total_bytes, chunk_bytes, T);
-  const int L = sg.lanes;
-  const bool mine = tid < L, last = tid == L - 1;
-  const uint32_t start = sg.begin + (uint32_t)(mine ? tid : 0) * (uint32_t)chunk_bytes;
-  const uint32_t limit = last ? 0xFFFFFFFFu : start + (uint32_t)chunk_bytes;
-
-  // ---- speculate, settle ----
-  JpegChunkState ent = jpeg_chunk_fresh(bytes, sg.begin, sg.end, start), ex = ent;
-  JpegChunkSum sum = {0u, 0u, 0u, 0u};
-  if (mine && !last) jpeg_chunk_speculate(bytes, sg.begin, sg.end, limit, q, s_huff, ent, ex, sum);
-  int rounds = 0;
-  for (int r = 0; r < L; ++r) {
-    if (mine) s_a[tid] = ex.pos, s_b[tid] = ex.bcz;
-    __syncthreads();
-    int changed = 0;
-    if (mine && tid > 0) {
-      JpegChunkState e;
-      e.pos = s_a[tid - 1], e.bcz = s_b[tid - 1];
-      if (!jpeg_chunk_same(e, ent)) {
-        ent = e, changed = 1;
-        if (!last) jpeg_chunk_speculate(bytes, sg.begin, sg.end, limit, q, s_huff, ent, ex, sum);
-      }
-    }
-    ++rounds;
-    if (!__syncthreads_or(changed)) break;
-  }
-
-  // ---- scan: inclusive over the lanes, then one to the left ----
-  if (!mine || last) sum.blocks = sum.dc0 = sum.dc1 = sum.dc2 = 0u;
-  s_a[tid] = sum.blocks, s_b[tid] = sum.dc0, s_c[tid] = sum.dc1, s_d[tid] = sum.dc2;
-  for (int off = 1; off < L; off <<= 1) {
-    __syncthreads();
-    uint32_t a = 0, b = 0, c = 0, d = 0;
-    if (tid >= off) a = s_a[tid - off], b = s_b[tid - off], c = s_c[tid - off], d = s_d[tid - off];
-    __syncthreads();
-    s_a[tid] += a, s_b[tid] += b, s_c[tid] += c, s_d[tid] += d;
-  }
-  __syncthreads();
-  uint32_t blk0 = 0, pred0 = 0, pred1 = 0, pred2 = 0;
-  if (tid > 0) blk0 = s_a[tid - 1], pred0 = s_b[tid - 1], pred1 = s_c[tid - 1], pred2 = s_d[tid - 1];
-  __syncthreads();
-
-  // ---- write ----
-  int st = JPEG_ST_OK;
-  uint32_t at = 0;
   const size_t plane = (size_t)g.Bw * g.Bh * 64;
-  if (mine)
-    st = jpeg_chunk_write(bytes, sg.begin, sg.end, total_bytes, limit, g, q, s_huff, s_zz, ent, blk0, pred0, pred1,
-                          pred2, sg.first_mcu, sg.n_blocks, sg.expect_rst, tid == 0, coef + (size_t)n * 3 * plane,
-                          &at);
-  s_a[tid] = st ? ((uint32_t)tid << 3 | (uint32_t)st) : 0xFFFFFFFFu;
-  for (int half = T >> 1; half > 0; half >>= 1) {
-    __syncthreads();
-    if (tid < half) s_a[tid] = min(s_a[tid], s_a[tid + half]);
-  }
-  if (tid == 0) {
-    seg_status[sidx] = s_a[0] == 0xFFFFFFFFu ? JPEG_ST_OK : (int32_t)(s_a[0] & 7u);
-    seg_rounds[sidx] = rounds;
-  }
+  jpeg_chunked_segment(bytes, total_bytes, g, segs, chunk_bytes, s_huff, s_zz, k, coef + (size_t)n * 3 * plane,
+                       seg_status, seg_rounds);
 }
 
 struct JscanLayout {

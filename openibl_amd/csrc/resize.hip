@@ -35,6 +35,7 @@
 #pragma clang fp contract(off)
 
 #include "augment_pixel.h"
+#include "jpeg_mixed.h"
 #include "resize_tables.h"
 
 namespace oibl {
@@ -64,13 +65,14 @@ static size_t resize_lds_bytes(const ResizeGeom& g) {
          (size_t)g.rows_cap * RS_ROW_BYTES;
 }
 
-// grid (ceil(W2 / RS_TILE_W), ceil(H2 / RS_TILE_H), N)
+// One tile of image n: blockIdx.x / blockIdx.y choose the tile, `img` is the image's [geo.H][geo.W][3] source and the
+// four tables are ITS tables, rows of geo.ksh / geo.ksv entries (resize_kernel: the batch's; resize_mixed_kernel: the
+// image's own, at the batch's largest row length).  Every thread of the workgroup calls it.
 template <int OUT_KIND>
-__global__ __launch_bounds__(RS_THREADS) void resize_kernel(const uint8_t* x, const int32_t* bounds_h,
-                                                            const int32_t* coeff_h, const int32_t* bounds_v,
-                                                            const int32_t* coeff_v, void* out, ResizeGeom geo,
-                                                            float m0, float m1, float m2, float s0, float s1,
-                                                            float s2) {
+__device__ __forceinline__ void resize_tile(const uint8_t* img, const int32_t* bounds_h, const int32_t* coeff_h,
+                                            const int32_t* bounds_v, const int32_t* coeff_v, void* out,
+                                            const ResizeGeom& geo, int n, float m0, float m1, float m2, float s0,
+                                            float s1, float s2) {
   extern __shared__ int32_t s_dyn[];   // resize_lds_bytes(geo)
   const int ksh = geo.ksh, ksv = geo.ksv;
   int32_t* s_ch = s_dyn;                         // [RS_TILE_W][ksh]
@@ -80,7 +82,7 @@ __global__ __launch_bounds__(RS_THREADS) void resize_kernel(const uint8_t* x, co
   uint8_t* s_mid = reinterpret_cast<uint8_t*>(s_bv + RS_TILE_H * 2);   // [rows_cap][RS_TILE_W][3]
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int ox0 = blockIdx.x * RS_TILE_W, oy0 = blockIdx.y * RS_TILE_H, n = blockIdx.z;
+  const int ox0 = blockIdx.x * RS_TILE_W, oy0 = blockIdx.y * RS_TILE_H;
   const int tw = min(RS_TILE_W, geo.W2 - ox0), th = min(RS_TILE_H, geo.H2 - oy0);
 
   for (int i = tid; i < tw * ksh; i += RS_THREADS) s_ch[i] = coeff_h[(size_t)ox0 * ksh + i];
@@ -93,7 +95,6 @@ __global__ __launch_bounds__(RS_THREADS) void resize_kernel(const uint8_t* x, co
   const int row0 = s_bv[0];
   const int rows = min(s_bv[2 * (th - 1)] + s_bv[2 * (th - 1) + 1] - row0, geo.rows_cap);
   const int row_bytes = tw * 3;
-  const uint8_t* img = x + (size_t)n * geo.H * geo.W * 3;
 
   // horizontal pass: source rows [row0, row0 + rows) -> s_mid [rows][RS_TILE_W][3]
   for (int r = wave; r < rows; r += RS_WAVES) {
@@ -135,6 +136,123 @@ __global__ __launch_bounds__(RS_THREADS) void resize_kernel(const uint8_t* x, co
       }
     }
   }
+}
+
+// grid (ceil(W2 / RS_TILE_W), ceil(H2 / RS_TILE_H), N)
+template <int OUT_KIND>
+__global__ __launch_bounds__(RS_THREADS) void resize_kernel(const uint8_t* x, const int32_t* bounds_h,
+                                                            const int32_t* coeff_h, const int32_t* bounds_v,
+                                                            const int32_t* coeff_v, void* out, ResizeGeom geo,
+                                                            float m0, float m1, float m2, float s0, float s1,
+                                                            float s2) {
+  const int n = blockIdx.z;
+  resize_tile<OUT_KIND>(x + (size_t)n * geo.H * geo.W * 3, bounds_h, coeff_h, bounds_v, coeff_v, out, geo, n, m0, m1,
+                        m2, s0, s1, s2);
+}
+
+// ---- a packed batch of mixed source sizes (oibl_resize_u8_mixed) ----------------------------------------------------
+// Image n is [H_n][W_n][3] at byte offset pix_n of one packed buffer; H_n, W_n and pix_n are row n of the decoder's
+// geometry table (jpeg_mixed.h).  Every image has tables of its own in the workspace, all with rows of the batch's
+// largest ksize per axis (ResizeMixGeom::ksh / ksv, from the host's copy of the sizes):
+//   bounds_h [N][W2][2], coeff_h [N][W2][ksh], bounds_v [N][H2][2], coeff_v [N][H2][ksv]
+// What the kernels read from the table is forced into range first: 1 <= H_n <= max_h, 1 <= W_n <= max_w (the largest
+// sides of the host's sizes, which sized the rows, the LDS and passed the scale limit — ksize and the rows of a tile
+// grow with the source size, so what holds for the largest holds for every image), and pix_n + 3 H_n W_n <=
+// packed_bytes.  An image that fails the check reads nothing: its tables are those of a 1 x 1 image and its output is
+// zero bytes (out_kind 0) or the normalised value of zero bytes (out_kind 1).
+struct ResizeMixGeom {
+  int H2, W2, ksh, ksv, rows_cap, max_h, max_w;
+  unsigned long long packed_bytes;
+  size_t bounds_h, coeff_h, bounds_v, coeff_v;   // int32 offsets into the workspace
+};
+
+struct ResizeMixImage {
+  int H, W, ok;
+  unsigned long long pix;
+};
+
+__device__ static inline ResizeMixImage resize_mixed_image(const int32_t* row, const ResizeMixGeom& mg) {
+  ResizeMixImage im;
+  const int h = row[JPEG_MIX_H], w = row[JPEG_MIX_W], hi = row[JPEG_MIX_PIX_HI];
+  im.H = min(max(h, 1), mg.max_h), im.W = min(max(w, 1), mg.max_w);
+  im.pix = (unsigned long long)(uint32_t)row[JPEG_MIX_PIX_LO] | (unsigned long long)(uint32_t)(hi & 0xFF) << 32;
+  im.ok = h == im.H && w == im.W && hi >= 0 && hi <= 0xFF &&
+          im.pix + (unsigned long long)im.H * (unsigned long long)im.W * 3 <= mg.packed_bytes;
+  if (!im.ok) im.H = im.W = 1, im.pix = 0;
+  return im;
+}
+
+// grid (ceil(max(W2, H2) / RS_THREADS), 2, N): blockIdx.y 0 the horizontal axis, 1 the vertical one
+__global__ __launch_bounds__(RS_THREADS) void resize_mixed_table_kernel(const int32_t* geom, ResizeMixGeom mg,
+                                                                        int32_t* ws) {
+  const int xx = blockIdx.x * RS_THREADS + threadIdx.x, n = blockIdx.z;
+  const bool vertical = blockIdx.y != 0;
+  const int out_size = vertical ? mg.H2 : mg.W2, ks = vertical ? mg.ksv : mg.ksh;
+  if (xx >= out_size) return;
+  const ResizeMixImage im = resize_mixed_image(geom + (size_t)n * JPEG_MIX_GEOM_INTS, mg);
+  const int in_size = vertical ? im.H : im.W;
+  const ResizeAxis a = rs_axis(in_size, out_size);   // a.ksize <= ks: in_size <= the largest, which gave ks
+  int32_t* bounds = ws + (vertical ? mg.bounds_v : mg.bounds_h) + ((size_t)n * out_size + xx) * 2;
+  int32_t* coeff = ws + (vertical ? mg.coeff_v : mg.coeff_h) + ((size_t)n * out_size + xx) * ks;
+  if (a.ksize > ks) {   // (unreachable; keeps the row inside its slot whatever the arithmetic says)
+    bounds[0] = 0, bounds[1] = 0;
+    return;
+  }
+  rs_table_row(a, in_size, xx, bounds, coeff);
+  for (int t = a.ksize; t < ks; ++t) coeff[t] = 0;
+}
+
+// grid (ceil(W2 / RS_TILE_W), ceil(H2 / RS_TILE_H), N)
+template <int OUT_KIND>
+__global__ __launch_bounds__(RS_THREADS) void resize_mixed_kernel(const uint8_t* packed, const int32_t* geom,
+                                                                  const int32_t* ws, void* out, ResizeMixGeom mg,
+                                                                  float m0, float m1, float m2, float s0, float s1,
+                                                                  float s2) {
+  const int n = blockIdx.z;
+  const ResizeMixImage im = resize_mixed_image(geom + (size_t)n * JPEG_MIX_GEOM_INTS, mg);
+  if (!im.ok) {   // the whole workgroup: the tile as zero bytes
+    const int ox0 = blockIdx.x * RS_TILE_W, oy0 = blockIdx.y * RS_TILE_H;
+    const int tw = min(RS_TILE_W, mg.W2 - ox0), th = min(RS_TILE_H, mg.H2 - oy0);
+    const float z[3] = {cj_normalize(0, m0, s0), cj_normalize(0, m1, s1), cj_normalize(0, m2, s2)};
+    for (int i = threadIdx.x; i < th * tw * 3; i += RS_THREADS) {
+      const int oy = i / (tw * 3), j = i - oy * tw * 3, col = j / 3, c = j - col * 3;
+      if (OUT_KIND == OIBL_JITTER_U8_NHWC)
+        ((uint8_t*)out)[(((size_t)n * mg.H2 + oy0 + oy) * mg.W2 + ox0) * 3 + j] = 0;
+      else
+        ((float*)out)[(((size_t)n * 3 + c) * mg.H2 + oy0 + oy) * mg.W2 + ox0 + col] = z[c];
+    }
+    return;
+  }
+  const ResizeGeom geo = {im.H, im.W, mg.H2, mg.W2, mg.ksh, mg.ksv, min(mg.rows_cap, im.H)};
+  resize_tile<OUT_KIND>(packed + im.pix, ws + mg.bounds_h + (size_t)n * mg.W2 * 2,
+                        ws + mg.coeff_h + (size_t)n * mg.W2 * mg.ksh, ws + mg.bounds_v + (size_t)n * mg.H2 * 2,
+                        ws + mg.coeff_v + (size_t)n * mg.H2 * mg.ksv, out, geo, n, m0, m1, m2, s0, s1, s2);
+}
+
+// the host's view of a mixed batch: the largest sides and what follows from them; false: a size or the scale limit
+static bool resize_mixed_geom(const int32_t* sizes, int N, int H2, int W2, ResizeMixGeom& mg, size_t& ws_bytes,
+                              int& bad) {
+  int max_h = 0, max_w = 0;
+  for (int n = 0; n < N; ++n) {
+    const int H = sizes[2 * n], W = sizes[2 * n + 1];
+    bad = n;
+    if (H < 1 || W < 1 || H > RS_MAX_DIM || W > RS_MAX_DIM) return false;
+    if ((long)H > (long)RS_MAX_SCALE * H2 || (long)W > (long)RS_MAX_SCALE * W2) return false;
+    max_h = H > max_h ? H : max_h, max_w = W > max_w ? W : max_w;
+  }
+  bad = -1;
+  mg.H2 = H2, mg.W2 = W2, mg.max_h = max_h, mg.max_w = max_w;
+  mg.ksh = rs_axis(max_w, W2).ksize, mg.ksv = rs_axis(max_h, H2).ksize;
+  const int rows = rs_tile_rows(rs_axis(max_h, H2));
+  mg.rows_cap = rows < max_h ? rows : max_h;
+  size_t at = 0;   // in int32s; every table starts on a multiple of 64 of them
+  mg.bounds_h = at, at += align_up((size_t)N * W2 * 2, 64);
+  mg.coeff_h = at, at += align_up((size_t)N * W2 * mg.ksh, 64);
+  mg.bounds_v = at, at += align_up((size_t)N * H2 * 2, 64);
+  mg.coeff_v = at, at += align_up((size_t)N * H2 * mg.ksv, 64);
+  ws_bytes = at * sizeof(int32_t);
+  mg.packed_bytes = 0;   // (the call's)
+  return true;
 }
 
 struct ResizeLayout {
@@ -236,6 +354,71 @@ int oibl_resize_u8(const uint8_t* x_nhwc, int N, int H, int W, int H2, int W2, i
     hipLaunchKernelGGL(resize_kernel<OIBL_JITTER_F32_NCHW>, grid, block, lds, st, x_nhwc, (const int32_t*)bounds_h,
                        (const int32_t*)coeff_h, (const int32_t*)bounds_v, (const int32_t*)coeff_v, out, geo,
                        mean3_host[0], mean3_host[1], mean3_host[2], std3_host[0], std3_host[1], std3_host[2]);
+  }
+  OIBL_LAUNCH_CHECK();
+  return OIBL_OK;
+}
+
+size_t oibl_resize_u8_mixed_workspace_bytes(const int32_t* sizes_host, int N, int H2, int W2) {
+  ResizeMixGeom mg;
+  size_t need = 0;
+  int bad = -1;
+  if (!sizes_host || N <= 0 || N > 65535 || H2 <= 0 || W2 <= 0 || H2 > RS_MAX_DIM || W2 > RS_MAX_DIM) return 0;
+  return resize_mixed_geom(sizes_host, N, H2, W2, mg, need, bad) ? need : 0;
+}
+
+int oibl_resize_u8_mixed(const uint8_t* packed, size_t packed_bytes, const int32_t* geom_dev,
+                         const int32_t* sizes_host, int N, int H2, int W2, int out_kind, const float* mean3_host,
+                         const float* std3_host, void* out, void* ws, size_t ws_bytes, void* stream) {
+  OIBL_REQUIRE(packed && geom_dev && sizes_host && out, "resize_u8_mixed: null pointer");
+  OIBL_REQUIRE(N > 0 && N <= 65535 && H2 > 0 && W2 > 0 && H2 <= RS_MAX_DIM && W2 <= RS_MAX_DIM,
+               "resize_u8_mixed: bad shape N=%d -> H2=%d W2=%d (N <= 65535, every size in [1, %d])", N, H2, W2,
+               RS_MAX_DIM);
+  OIBL_REQUIRE(packed_bytes >= 1 && packed_bytes < JPEG_MIX_MAX_PIXEL_BYTES,
+               "resize_u8_mixed: packed_bytes %zu must be in [1, 2^40)", packed_bytes);
+  ResizeMixGeom mg;
+  size_t need = 0;
+  int bad = -1;
+  const bool fits = resize_mixed_geom(sizes_host, N, H2, W2, mg, need, bad);
+  OIBL_REQUIRE(fits || (sizes_host[2 * bad] >= 1 && sizes_host[2 * bad + 1] >= 1 &&
+                        sizes_host[2 * bad] <= RS_MAX_DIM && sizes_host[2 * bad + 1] <= RS_MAX_DIM),
+               "resize_u8_mixed: bad shape: image %d is %d x %d, every size must be in [1, %d]", bad,
+               sizes_host[2 * bad], sizes_host[2 * bad + 1], RS_MAX_DIM);
+  OIBL_REQUIRE(fits, "resize_u8_mixed: image %d: %d x %d -> %d x %d shrinks an axis by more than the limit of %d (the "
+               "source rows of a tile must fit in LDS)", bad, sizes_host[2 * bad], sizes_host[2 * bad + 1], H2, W2,
+               RS_MAX_SCALE);
+  OIBL_REQUIRE(out_kind == OIBL_JITTER_U8_NHWC || out_kind == OIBL_JITTER_F32_NCHW,
+               "resize_u8_mixed: unknown out_kind %d", out_kind);
+  OIBL_REQUIRE(out_kind == OIBL_JITTER_U8_NHWC || (mean3_host && std3_host),
+               "resize_u8_mixed: the fp32 output needs mean3_host and std3_host");
+  OIBL_REQUIRE(out_kind == OIBL_JITTER_U8_NHWC || (uintptr_t)out % 4 == 0,
+               "resize_u8_mixed: the fp32 output must be 4-byte aligned");
+  OIBL_REQUIRE((uintptr_t)geom_dev % 4 == 0, "resize_u8_mixed: geom_dev must be 4-byte aligned");
+  OIBL_REQUIRE(ws && (uintptr_t)ws % 256 == 0, "resize_u8_mixed: workspace must be 256-byte aligned");
+  if (ws_bytes < need) {
+    set_error("resize_u8_mixed: workspace %zu < required %zu bytes", ws_bytes, need);
+    return OIBL_E_WORKSPACE;
+  }
+  mg.packed_bytes = packed_bytes;
+  const ResizeGeom largest = {mg.max_h, mg.max_w, H2, W2, mg.ksh, mg.ksv, mg.rows_cap};
+  const size_t lds = resize_lds_bytes(largest);
+  OIBL_REQUIRE(lds <= 65536, "resize_u8_mixed: %zu bytes of LDS per workgroup", lds);   // implied by the scale limit
+  hipStream_t st = (hipStream_t)stream;
+  int32_t* tables = (int32_t*)ws;
+  const int longest = H2 > W2 ? H2 : W2;
+  hipLaunchKernelGGL(resize_mixed_table_kernel,
+                     dim3((unsigned)((longest + RS_THREADS - 1) / RS_THREADS), 2u, (unsigned)N), dim3(RS_THREADS), 0,
+                     st, geom_dev, mg, tables);
+  OIBL_LAUNCH_CHECK();
+  const dim3 grid((unsigned)((W2 + RS_TILE_W - 1) / RS_TILE_W), (unsigned)((H2 + RS_TILE_H - 1) / RS_TILE_H),
+                  (unsigned)N), block(RS_THREADS);
+  if (out_kind == OIBL_JITTER_U8_NHWC) {
+    hipLaunchKernelGGL(resize_mixed_kernel<OIBL_JITTER_U8_NHWC>, grid, block, lds, st, packed, geom_dev,
+                       (const int32_t*)tables, out, mg, 0.0f, 0.0f, 0.0f, 1.0f, 1.0f, 1.0f);
+  } else {
+    hipLaunchKernelGGL(resize_mixed_kernel<OIBL_JITTER_F32_NCHW>, grid, block, lds, st, packed, geom_dev,
+                       (const int32_t*)tables, out, mg, mean3_host[0], mean3_host[1], mean3_host[2], std3_host[0],
+                       std3_host[1], std3_host[2]);
   }
   OIBL_LAUNCH_CHECK();
   return OIBL_OK;

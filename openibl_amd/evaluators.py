@@ -104,10 +104,11 @@ def _extract_local(model, data_loader, vlad, pca, gpu, print_freq, rank, scales=
     with torch.no_grad():
         for i, batch in enumerate(data_loader):
             imgs = batch[0]
+            mixed = bool(input_decode) and extract.is_mixed_batch(imgs)
             if input_decode:
                 imgs = extract.apply_input_decode(imgs, _device(gpu), decoded, extract._batch_names(batch),
-                                                  scan=scan_route(input_decode))
-            if resize is not None:
+                                                  scan=scan_route(input_decode), resize=resize)
+            if resize is not None and not mixed:
                 imgs = extract.apply_input_resize(resize, torch.as_tensor(imgs), _device(gpu))
             data_t.update(time.time() - end)
             out = extract_cnn_feature(model, imgs, vlad, gpu=gpu, scales=scales)

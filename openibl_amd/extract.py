@@ -586,14 +586,36 @@ def apply_input_resize(resize, imgs: torch.Tensor, dev) -> torch.Tensor:
     return resize(imgs.contiguous().to(dev, non_blocking=True))
 
 
-def apply_input_decode(batch0, dev, pending, names=None, scan="auto") -> torch.Tensor:
+def is_mixed_batch(batch0) -> bool:
+    """Is a loader's item 0 a `openibl_amd.jpeg.MixedJpegBatch` (`apply_input_decode` then resizes it as well)?"""
+    from .jpeg import MixedJpegBatch
+    return isinstance(batch0, MixedJpegBatch)
+
+
+def apply_input_decode(batch0, dev, pending, names=None, scan="auto", resize=None) -> torch.Tensor:
     """A loader's `openibl_amd.jpeg.JpegBatch` (host, pinned or not) -> the decoded uint8 batch [N][H][W][3] on the
     device, computed on the current stream (`ops.decode_jpeg`; a temporary of that stream, like the result of
     `apply_input_resize`).  Nothing is read back: the per-image status stays on the device and is appended to
     `pending` with the batch's file names, for `check_input_decode` when the loop has ended.  scan: the route of
-    `ops.decode_jpeg` ("auto", "serial", "chunked")."""
+    `ops.decode_jpeg` ("auto", "serial", "chunked").
+    A `openibl_amd.jpeg.MixedJpegBatch` (files of mixed stored sizes, `jpeg.collate_mixed`) is decoded AND resized in
+    this one step (`ops.decode_resize_jpeg`), because only the resized images form a batch: `resize` is then the
+    caller's `input_resizer(input_resize)` and must be a fixed target — ValueError without one and for
+    keep_aspect=True, whose outputs would differ in size.  The caller skips its own resize for such a batch
+    (`is_mixed_batch`); what it gets is the dense uint8 batch [N][h][w][3]."""
     from . import ops
     from .jpeg import JpegBatch
+    if is_mixed_batch(batch0):
+        if resize is None:
+            raise ValueError("input_decode: a MixedJpegBatch (files of mixed stored sizes) needs input_resize=(height, "
+                             "width): only the resized images form a batch")
+        if getattr(resize, "keep_aspect", False):
+            raise ValueError("input_decode: a MixedJpegBatch cannot be resized with keep_aspect=True: the images of "
+                             "one batch would get different sizes")
+        pixels, status = ops.decode_resize_jpeg(batch0.to(dev, non_blocking=True), (resize.height, resize.width),
+                                                out="uint8", check=False, scan=scan)
+        pending.append((status, None if names is None else list(names)))
+        return pixels
     if not isinstance(batch0, JpegBatch):
         raise ValueError(f"input_decode=True decodes JpegBatch batches (a loader over Preprocessor(..., raw=True) "
                          f"with collate_fn=openibl_amd.jpeg.collate), got {type(batch0).__name__}")
@@ -612,7 +634,7 @@ def check_input_decode(pending) -> None:
         for i, s in enumerate(status.cpu().tolist()):
             if s:
                 who = names[i] if names is not None and i < len(names) else f"item {at + i}"
-                bad.append(f"{who} ({STATUS_TEXT[min(int(s), 4)]})")
+                bad.append(f"{who} ({STATUS_TEXT[min(int(s), len(STATUS_TEXT) - 1)]})")
         at += int(status.numel())
     del pending[:]
     if bad:
@@ -636,7 +658,8 @@ def extract_descriptors(model, data_loader, vlad=True, pca=None, gpu=None, print
     of every batch is an `openibl_amd.jpeg.JpegBatch` (the files' bytes, parsed by the loader's workers) and is decoded
     on the device in front of the resize; the statuses are read once, when the loop has ended, and a RuntimeError
     then lists the damaged files.  `input_decode` may also name the route of `ops.decode_jpeg` ("serial", "chunked";
-    True is "auto")."""
+    True is "auto").  A loader with `collate_fn=jpeg.collate_mixed` yields `jpeg.MixedJpegBatch` batches — files of
+    mixed stored sizes — which need `input_resize=(height, width)` and are decoded and resized in one step."""
     from .jpeg import scan_route
     core = unwrap_model(model)
     decoded = []
@@ -663,11 +686,13 @@ def extract_descriptors(model, data_loader, vlad=True, pca=None, gpu=None, print
     with torch.no_grad():
         for i, batch in enumerate(data_loader):
             imgs = batch[0]
+            mixed = bool(input_decode) and is_mixed_batch(imgs)     # decoded and resized in one step
             if input_decode:
-                imgs = apply_input_decode(imgs, dev, decoded, _batch_names(batch), scan=scan_route(input_decode))
+                imgs = apply_input_decode(imgs, dev, decoded, _batch_names(batch), scan=scan_route(input_decode),
+                                          resize=resize)
             if not torch.is_tensor(imgs):
                 imgs = torch.as_tensor(imgs)
-            if resize is not None:
+            if resize is not None and not mixed:
                 imgs = apply_input_resize(resize, imgs, dev)
             if imgs.dtype != torch.uint8 and imgs.dtype != torch.float32:
                 imgs = imgs.float()

@@ -7,6 +7,9 @@ the DataLoader collate function.  Pure numpy; Pillow is needed only for a file t
                       `Preprocessor(..., raw=True)`): parsed in the worker, unsupported files decoded there with PIL
     JpegBatch      packed scan bytes, records and the segment table as tensors (pinnable), the host-decoded
                    fallbacks as pixels; `.to(device)`; `ops.decode_jpeg(batch)` gives [N][H][W][3] uint8
+    MixedJpegBatch / collate_mixed
+                   the same for files of MIXED stored sizes, with the per-image geometry table of
+                   csrc/jpeg_mixed.h; `ops.decode_resize_jpeg(batch, (h, w))` gives the dense [N][h][w][3] uint8
 
 The device decodes baseline JPEG (SOF0, 8 bit) with one scan holding all components, one component or three with the
 ids 1, 2, 3, luma factors (1,1), (2,1) or (2,2) over chroma (1,1), 8-bit quantisation tables, at most two DC and two
@@ -24,9 +27,9 @@ import torch
 REC_BYTES = 1408              # JPEG_REC_BYTES of csrc/jpeg_entropy.h: int32 header[16], qt[4][64], huff[4][272]
 REC_QT, REC_HUFF, HUFF_BYTES = 64, 320, 272
 MAX_DIM, MIN_WIDTH = 32768, 8
-ST_OK, ST_BAD_CODE, ST_OVERRUN, ST_OUT_OF_BYTES, ST_BAD_RESTART = range(5)
+ST_OK, ST_BAD_CODE, ST_OVERRUN, ST_OUT_OF_BYTES, ST_BAD_RESTART, ST_BAD_GEOM = range(6)
 STATUS_TEXT = ("ok", "bad Huffman code", "coefficient index above 63", "ran out of bytes",
-               "restart marker missing or wrong")
+               "restart marker missing or wrong", "geometry table inconsistent")
 # The chunked route of `ops.decode_jpeg` (csrc/jpeg_chunked.hip): many lanes inside one segment.  scan="auto" takes it
 # when the batch's longest segment has at least CHUNKED_MIN_BYTES bytes; a lane's chunk has CHUNK_BYTES raw bytes, more
 # where a segment would otherwise have more than MAX_CHUNK_LANES chunks.  Both are set from one run on an MI355X
@@ -338,6 +341,177 @@ class JpegBatch:
                    max_bytes)
 
 
+# ---- batches of mixed stored sizes (csrc/jpeg_mixed.h, csrc/jpeg_mixed.hip) ------------------------------------------
+GEOM_INTS = 8                 # JPEG_MIX_GEOM_INTS: H, W, coefficient base, plane base, pixel offset low / high, 0, 0
+PIX_ALIGN = 64                # JPEG_MIX_PIX_ALIGN: every image of the packed pixels starts on a multiple of it
+MAX_SHRINK = 16               # RS_MAX_SCALE of csrc/resize_tables.h: the largest stored / target size per axis
+
+
+def mixed_layout(sizes):
+    """jpeg_mixed_layout of csrc/jpeg_mixed.h in numpy (a loader's worker lays its batch out without loading the
+    library; tests/test_jpeg_mixed_cpu.py holds it to `oibl_jpeg_mixed_layout`): sizes int [N][2] = {H, W} ->
+    (geom int32 [N][GEOM_INTS], totals): the images back to back in the coefficients, the sample planes and the packed
+    pixels.  totals = (coefficient bytes, plane bytes, packed pixel bytes, largest Bw * Bh, largest H, largest W)."""
+    sizes = np.asarray(sizes, dtype=np.int64).reshape(-1, 2)
+    N = sizes.shape[0]
+    if not 1 <= N <= 65535:
+        raise ValueError(f"mixed_layout: N = {N} must be in [1, 65535]")
+    bad = np.flatnonzero((sizes < 1).any(1) | (sizes > MAX_DIM).any(1))
+    if bad.size:
+        i = int(bad[0])
+        raise ValueError(f"mixed_layout: image {i} is {sizes[i, 0]} x {sizes[i, 1]}, every side must be in "
+                         f"[1, {MAX_DIM}]")
+    H, W = sizes[:, 0], sizes[:, 1]
+    bb = (2 * ((W + 15) // 16)) * (2 * ((H + 15) // 16))
+    blocks = np.concatenate([[0], np.cumsum(3 * bb)])
+    if blocks[-1] >= 1 << 31:
+        raise ValueError(f"mixed_layout: 2^31 coefficient blocks or more at image "
+                         f"{int(np.argmax(blocks[1:] >= 1 << 31))}")
+    pix = np.zeros(N, np.int64)
+    end = 0
+    for i in range(N):
+        pix[i] = -(-end // PIX_ALIGN) * PIX_ALIGN
+        end = int(pix[i] + 3 * H[i] * W[i])
+        if end >= 1 << 40:
+            raise ValueError(f"mixed_layout: 2^40 packed pixel bytes or more at image {i}")
+    geom = np.zeros((N, GEOM_INTS), np.int32)
+    geom[:, 0], geom[:, 1], geom[:, 2], geom[:, 3] = H, W, blocks[:-1], blocks[:-1]
+    geom[:, 4] = (pix & 0xFFFFFFFF).astype(np.uint32).view(np.int32)
+    geom[:, 5] = pix >> 32
+    return geom, (int(blocks[-1]) * 128, int(blocks[-1]) * 64, end, int(bb.max()), int(H.max()), int(W.max()))
+
+
+def geom_pixel_offsets(geom) -> np.ndarray:
+    """int64 [N]: every image's byte offset in the packed pixels, from a geometry table (numpy or a host tensor)."""
+    g = geom.numpy() if torch.is_tensor(geom) else np.asarray(geom)
+    return g[:, 4].astype(np.int64) & 0xFFFFFFFF | g[:, 5].astype(np.int64) << 32
+
+
+def check_shrink(sizes, target, what="MixedJpegBatch") -> None:
+    """ValueError for the first image a resize to target = (h, w) would shrink by more than MAX_SHRINK on an axis."""
+    h2, w2 = int(target[0]), int(target[1])
+    if h2 < 1 or w2 < 1:
+        raise ValueError(f"{what}: the target size must be positive, got {h2} x {w2}")
+    for i, (h, w) in enumerate(np.asarray(sizes).reshape(-1, 2).tolist()):
+        if h > MAX_SHRINK * h2 or w > MAX_SHRINK * w2:
+            raise ValueError(f"{what}: image {i} is {h} x {w}: a resize to {h2} x {w2} shrinks an axis by more than "
+                             f"the limit of {MAX_SHRINK}")
+
+
+class MixedJpegBatch:
+    """N stored images of ANY sizes on their way to `ops.decode_resize_jpeg` / `ops.decode_jpeg_mixed`.  As in a
+    JpegBatch the images the device decodes (batch positions `dev_index`) travel as `scan`, `records` and `segments`,
+    the others (`host_index`; `reasons[i]` says why) as pixels decoded on the host: `host_pixels`, ONE packed uint8
+    tensor, image j of them at `host_offsets[j]` — the flow never fails because of a file's format.
+      sizes       int32 [N][2] = {H, W}, always on the host (the C calls size their grids and tables from it)
+      geom        int32 [N][GEOM_INTS]: the layout of all N images (`mixed_layout`): where image i lies in the packed
+                  pixel buffer of `totals[2]` bytes that the decoder writes and the resize reads; `geom_host` is its
+                  copy that stays on the host (numpy)
+      dev_geom    int32 [Nd][GEOM_INTS]: the rows of the device-decoded images as `oibl_jpeg_decode_mixed` takes
+                  them — their coefficient and plane bases from a layout of those images alone (`dev_totals`), their
+                  pixel offsets from `geom`
+    `max_segments`, `max_segment_bytes`: as for JpegBatch."""
+
+    _TENSORS = ("scan", "records", "segments", "dev_index", "host_index", "host_pixels", "geom", "dev_geom")
+
+    def __init__(self, n, sizes, geom, totals, dev_geom, dev_totals, scan, records, segments, max_segments, dev_index,
+                 host_index, host_pixels, host_offsets, reasons, max_segment_bytes=0):
+        self.n = int(n)
+        self.sizes, self.geom, self.totals = sizes, geom, tuple(int(v) for v in totals)
+        # the host's copy of the table (numpy, never moved): where the views and the host-decoded slots lie
+        self.geom_host = geom.cpu().numpy().copy()
+        self.dev_geom, self.dev_totals = dev_geom, tuple(int(v) for v in dev_totals)
+        self.scan, self.records, self.segments = scan, records, segments
+        self.max_segments, self.max_segment_bytes = int(max_segments), int(max_segment_bytes)
+        self.dev_index, self.host_index = dev_index, host_index
+        self.host_pixels, self.host_offsets = host_pixels, tuple(int(v) for v in host_offsets)
+        self.reasons = tuple(reasons)
+
+    def __len__(self):
+        return self.n
+
+    @property
+    def is_cuda(self):
+        return self.geom.is_cuda
+
+    @property
+    def device(self):
+        return self.geom.device
+
+    @property
+    def uniform(self) -> bool:
+        """Do all images have one stored size?"""
+        return bool((self.sizes == self.sizes[0]).all())
+
+    def _map(self, fn):
+        out = MixedJpegBatch.__new__(MixedJpegBatch)
+        out.__dict__.update(self.__dict__)
+        for name in self._TENSORS:
+            setattr(out, name, fn(getattr(self, name)))
+        return out
+
+    def to(self, device, non_blocking=False):
+        return self._map(lambda t: t.to(device, non_blocking=non_blocking))
+
+    def cuda(self, device=None, non_blocking=False):
+        dev = torch.device("cuda", torch.cuda.current_device() if device is None else device) \
+            if not isinstance(device, torch.device) else device
+        return self.to(dev, non_blocking=non_blocking)
+
+    def pin_memory(self):
+        return self._map(lambda t: t.pin_memory() if t.numel() else t)
+
+    def is_pinned(self):
+        return all(getattr(self, name).is_pinned() for name in self._TENSORS if getattr(self, name).numel())
+
+    @classmethod
+    def from_files(cls, files, target=None) -> "MixedJpegBatch":
+        """files: the bytes of N files (bytes, numpy or 1-D uint8 tensors) of any stored sizes.  target = (h, w): the
+        size the batch will be resized to; an image beyond the resize's per-axis shrink limit then raises ValueError
+        here, in the loader's worker (without it the device call raises).  A file with a side above MAX_DIM = 32768
+        — only a host-decoded one can have it, a PNG for instance — is a ValueError as well: neither the layout nor
+        the resize takes it, as `ops.resize_u8` does not."""
+        files = list(files)
+        if not files:
+            raise ValueError("MixedJpegBatch: an empty batch")
+        scans, recs, segs, dev_idx, host_idx, host_px, reasons, sizes = [], [], [], [], [], [], [], []
+        at = nseg = max_seg = max_bytes = 0
+        for i, f in enumerate(files):
+            p = parse(f)
+            reasons.append(p.reason)
+            if p.device:
+                if at + p.scan.size >= 1 << 31:
+                    raise ValueError(f"MixedJpegBatch: more than 2^31 scan bytes in one batch (at image {i})")
+                rec, sg = p.record.copy(), p.segments + np.int32(at)
+                rec[:64].view(np.int32)[13] = nseg
+                scans.append(p.scan), recs.append(rec), segs.append(sg), dev_idx.append(i)
+                at, nseg, max_seg = at + p.scan.size, nseg + sg.shape[0], max(max_seg, sg.shape[0])
+                max_bytes = max(max_bytes, int((sg[:, 1] - sg[:, 0]).max()))
+                sizes.append((p.height, p.width))
+            else:
+                px = np.ascontiguousarray(decode_on_host(f))
+                host_idx.append(i), host_px.append(px.reshape(-1))
+                sizes.append(px.shape[:2])
+        sizes = np.asarray(sizes, np.int32).reshape(-1, 2)
+        if target is not None:
+            check_shrink(sizes, target)
+        geom, totals = mixed_layout(sizes)
+        if dev_idx:
+            dev_geom, dev_totals = mixed_layout(sizes[dev_idx])
+            dev_geom[:, 4:6] = geom[dev_idx, 4:6]
+            dev_totals = dev_totals[:2] + (totals[2],) + dev_totals[3:]
+        else:
+            dev_geom, dev_totals = np.zeros((0, GEOM_INTS), np.int32), (0, 0, totals[2], 0, 0, 0)
+        t = torch.from_numpy
+        return cls(len(files), t(sizes), t(geom), totals, t(dev_geom), dev_totals,
+                   t(np.concatenate(scans)) if scans else torch.empty(0, dtype=torch.uint8),
+                   t(np.stack(recs)) if recs else torch.empty((0, REC_BYTES), dtype=torch.uint8),
+                   t(np.concatenate(segs)) if segs else torch.empty((0, 2), dtype=torch.int32),
+                   max_seg, torch.tensor(dev_idx, dtype=torch.int64), torch.tensor(host_idx, dtype=torch.int64),
+                   t(np.concatenate(host_px)) if host_px else torch.empty(0, dtype=torch.uint8),
+                   np.concatenate([[0], np.cumsum([p.size for p in host_px])]).astype(np.int64), reasons, max_bytes)
+
+
 def scan_route(input_decode) -> str:
     """The `scan` of `ops.decode_jpeg` an `input_decode` argument asks for: a route's name is itself, anything else
     that is true is "auto"."""
@@ -357,3 +531,15 @@ def collate(items):
         return JpegBatch.from_files(items)
     rest = default_collate([tuple(it[1:]) for it in items]) if len(first) > 1 else []
     return [JpegBatch.from_files([it[0] for it in items])] + list(rest)
+
+
+def collate_mixed(items, target=None):
+    """`collate` for files of mixed stored sizes: item 0 of the batch is a MixedJpegBatch, the other fields are
+    collated as usual.  target = (h, w), the size of the resize behind the decoder, makes an image beyond the resize's
+    shrink limit a ValueError in the worker: `collate_fn=functools.partial(jpeg.collate_mixed, target=(480, 640))`."""
+    from torch.utils.data import default_collate
+    first = items[0]
+    if torch.is_tensor(first) or isinstance(first, (bytes, bytearray, np.ndarray)):
+        return MixedJpegBatch.from_files(items, target=target)
+    rest = default_collate([tuple(it[1:]) for it in items]) if len(first) > 1 else []
+    return [MixedJpegBatch.from_files([it[0] for it in items], target=target)] + list(rest)

@@ -199,6 +199,13 @@ SIGNATURES = {
     "oibl_jpeg_decode_chunked_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "oibl_jpeg_decode_chunked": (c_int, [c_void_p, c_size_t, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
                                          c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "oibl_jpeg_mixed_layout": (c_int, [c_void_p, c_int, c_void_p, c_void_p]),
+    "oibl_jpeg_decode_mixed_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
+    "oibl_jpeg_decode_mixed": (c_int, [c_void_p, c_size_t, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
+                                       c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "oibl_resize_u8_mixed_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int]),
+    "oibl_resize_u8_mixed": (c_int, [c_void_p, c_size_t, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p,
+                                     c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "oibl_cluster_means": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "oibl_local_descriptors": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     "oibl_assign_gap_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),

@@ -149,7 +149,8 @@ def update_sampler(sampler, model, loader, query, gallery, sub_set, rerank=False
     input_resize: as in `extract_features` — `loader` delivers raw uint8 batches at their stored size, resized on the
     device (a trunk cache was filled behind the same resize: `TrunkCache.fill(..., input_resize=...)`).
     input_decode: as in `extract_features` — `loader` delivers the files' bytes as JpegBatch batches, decoded on the
-    device in front of the resize."""
+    device in front of the resize; MixedJpegBatch batches (files of mixed stored sizes, `jpeg.collate_mixed`) need
+    input_resize=(height, width) and are decoded and resized in one step."""
     from .evaluators import _extract_local, _rank_world
     rank, world = _rank_world()
     if world != 1:

@@ -2168,3 +2168,194 @@ def decode_jpeg(batch, check: bool = True, scan: str = "auto", chunk_bytes=None)
         raise ValueError("decode_jpeg: damaged JPEG streams: " + ", ".join(
             f"image {i} ({_jpeg.STATUS_TEXT[min(int(s), 4)]})" for i, s in enumerate(bad) if s))
     return pixels
+
+
+# ---------------------------------------------------------------------------------------------
+def _mixed_sizes(sizes, what: str):
+    """sizes (tensor, numpy or a list of (H, W)) -> a contiguous int32 [N][2] numpy array on the host."""
+    import numpy as np
+    if torch.is_tensor(sizes):
+        sizes = sizes.cpu().numpy()
+    sizes = np.ascontiguousarray(np.asarray(sizes, dtype=np.int32).reshape(-1, 2))
+    if sizes.shape[0] < 1:
+        raise ValueError(f"{what}: an empty batch")
+    return sizes
+
+
+def _totals6(totals):
+    return (C.c_size_t * 6)(*[int(v) for v in totals])
+
+
+def _decode_jpeg_mixed_packed(batch, scan, chunk_bytes):
+    """The packed pixel buffer (uint8 [batch.totals[2]]) and the statuses (int32 [N]) of a MixedJpegBatch on the
+    device: one decoder call for the device-decoded images, one copy per host-decoded image into its slot."""
+    global last_jpeg_route, last_jpeg_rounds
+    from . import jpeg as _jpeg
+    if not isinstance(batch, _jpeg.MixedJpegBatch):
+        raise ValueError(f"decode_jpeg_mixed expects a MixedJpegBatch (openibl_amd.jpeg.collate_mixed), got "
+                         f"{type(batch).__name__}")
+    if scan not in _jpeg.SCAN_ROUTES:
+        raise ValueError(f"decode_jpeg_mixed: scan must be one of {_jpeg.SCAN_ROUTES}, not {scan!r}")
+    if chunk_bytes is not None and not 4 <= int(chunk_bytes) <= 65536:
+        raise ValueError(f"decode_jpeg_mixed: chunk_bytes {chunk_bytes} must be in [4, 65536]")
+    dev = _need_cuda(batch.scan, batch.records, batch.segments, batch.host_pixels, batch.dev_index,
+                     batch.host_index, batch.geom, batch.dev_geom)
+    N = batch.n
+    nd, nh = int(batch.records.shape[0]), int(batch.host_index.shape[0])
+    if nd + nh != N or batch.records.shape[1:] != (_jpeg.REC_BYTES,) or tuple(batch.sizes.shape) != (N, 2) or \
+            tuple(batch.geom.shape) != (N, _jpeg.GEOM_INTS) or tuple(batch.dev_geom.shape) != (nd, _jpeg.GEOM_INTS) or \
+            len(batch.host_offsets) != nh + 1 or batch.host_offsets[-1] != batch.host_pixels.numel():
+        raise ValueError(f"decode_jpeg_mixed: inconsistent batch: {nd} records + {nh} host images for N = {N}")
+    packed = torch.empty(batch.totals[2], dtype=torch.uint8, device=dev)
+    status = torch.zeros(N, dtype=torch.int32, device=dev)
+    if nd:
+        lib = _lib.load()
+        S = int(batch.segments.shape[0])
+        st = status if nh == 0 else torch.empty(nd, dtype=torch.int32, device=dev)
+        if scan == "auto":
+            scan = "chunked" if batch.max_segment_bytes >= _jpeg.CHUNKED_MIN_BYTES else "serial"
+        cb = 0
+        if scan == "chunked":
+            cb = int(chunk_bytes) if chunk_bytes is not None else \
+                min(65536, max(_jpeg.CHUNK_BYTES, -(-batch.max_segment_bytes // _jpeg.MAX_CHUNK_LANES)))
+        totals = _totals6(batch.dev_totals)
+        need = lib.oibl_jpeg_decode_mixed_workspace_bytes(totals, nd, S)
+        if need == 0:
+            raise ValueError(f"decode_jpeg_mixed: {nd} images, {S} segments, totals {batch.dev_totals}: outside the "
+                             f"decoder's limits (at most 65535 images of at least {_jpeg.MIN_WIDTH} and at most "
+                             f"{_jpeg.MAX_DIM} pixels per side)")
+        ws = workspace(need, dev, slot="jpeg_decode")
+        _lib.check(lib.oibl_jpeg_decode_mixed(_ptr(batch.scan), batch.scan.numel(), _ptr(batch.records),
+                                              _ptr(batch.segments), S, batch.max_segments, nd, _ptr(batch.dev_geom),
+                                              totals, cb, _ptr(packed), _ptr(st), _ptr(ws), ws.numel(),
+                                              _stream(dev)), "jpeg_decode_mixed")
+        # the workspace: the coefficients, int32 segment status [S], int32 rounds [S], the planes
+        at = _align256(batch.dev_totals[0]) + _align256(4 * S)
+        last_jpeg_rounds = ws[at:at + 4 * S].view(torch.int32) if cb else None
+        last_jpeg_route = scan
+        if nh:
+            status[batch.dev_index] = st
+    if nh:
+        offs = _jpeg.geom_pixel_offsets(batch.geom_host)
+        sizes = batch.sizes.tolist()
+        for j, i in enumerate(_mixed_host_index(batch)):
+            n = 3 * sizes[i][0] * sizes[i][1]
+            packed[int(offs[i]):int(offs[i]) + n] = batch.host_pixels[batch.host_offsets[j]:batch.host_offsets[j] + n]
+    return packed, status
+
+
+def _mixed_host_index(batch):
+    """The batch positions of the host-decoded images, from `reasons` (host data: no read-back)."""
+    return [i for i, r in enumerate(batch.reasons) if r]
+
+
+def _mixed_views(packed, batch):
+    from . import jpeg as _jpeg
+    offs = _jpeg.geom_pixel_offsets(batch.geom_host)
+    return [packed[int(o):int(o) + 3 * h * w].view(h, w, 3) for o, (h, w) in zip(offs, batch.sizes.tolist())]
+
+
+def _raise_damaged(what, status):
+    from . import jpeg as _jpeg
+    bad = status.cpu().numpy()
+    if bad.any():
+        raise ValueError(f"{what}: damaged JPEG streams: " + ", ".join(
+            f"image {i} ({_jpeg.STATUS_TEXT[min(int(s), len(_jpeg.STATUS_TEXT) - 1)]})"
+            for i, s in enumerate(bad) if s))
+
+
+def decode_jpeg_mixed(batch, check: bool = True, scan: str = "auto", chunk_bytes=None):
+    """Decode a `openibl_amd.jpeg.MixedJpegBatch` — N files of any stored sizes — on the device
+    (oibl_jpeg_decode_mixed): a list of N uint8 views [H_i][W_i][3] into ONE packed buffer, each the bytes of
+    `np.asarray(Image.open(f).convert('RGB'))`.  All images' segments decode in one launch; the files the device does
+    not decode were decoded on the host when the batch was built and are copied into their slots.  scan, chunk_bytes
+    and check as for `decode_jpeg` ("auto" looks at the batch's longest segment); check=False returns
+    (views, status): status int32 [N] on the device, 0 ok, 5 for an image whose row of the geometry table is
+    inconsistent (`jpeg.STATUS_TEXT`)."""
+    packed, status = _decode_jpeg_mixed_packed(batch, scan, chunk_bytes)
+    views = _mixed_views(packed, batch)
+    if not check:
+        return views, status
+    _raise_damaged("decode_jpeg_mixed", status)
+    return views
+
+
+def resize_u8_mixed(packed: torch.Tensor, sizes, size, out: str = "uint8", mean=REF_MEAN, std=REF_STD) -> torch.Tensor:
+    """Bilinear resize of a PACKED batch of mixed source sizes on the device (oibl_resize_u8_mixed), PIL's bits:
+    packed is a 1-D uint8 tensor that holds image i as [H_i][W_i][3] at the offset `jpeg.mixed_layout(sizes)` gives it
+    (what `decode_jpeg_mixed` writes), sizes int [N][2] = {H_i, W_i} on the host, size = (height, width) of the
+    result.  out='uint8': [N][height][width][3]; out='float': [N][3][height][width] float32, ToTensor + Normalize of
+    those bytes.  Every image equals `resize_u8` of that image alone; the per-axis shrink limit RESIZE_MAX_SCALE holds
+    per image."""
+    from . import jpeg as _jpeg
+    if out not in JITTER_OUT:
+        raise ValueError(f"resize_u8_mixed: out must be 'float' or 'uint8', not {out!r}")
+    if packed.dtype != torch.uint8 or packed.dim() != 1:
+        raise ValueError(f"resize_u8_mixed expects a 1-D uint8 packed buffer, got {packed.dtype} {tuple(packed.shape)}")
+    if not isinstance(size, (tuple, list)) or len(size) != 2:
+        raise ValueError(f"resize_u8_mixed: size must be (height, width), got {size!r}")
+    H2, W2 = int(size[0]), int(size[1])
+    sizes = _mixed_sizes(sizes, "resize_u8_mixed")
+    N = sizes.shape[0]
+    if H2 < 1 or W2 < 1:
+        raise ValueError(f"resize_u8_mixed: the target size must be positive, got {H2} x {W2}")
+    if max(H2, W2) > RESIZE_MAX_DIM or N > 65535:
+        raise ValueError(f"resize_u8_mixed: N <= 65535 and every size <= {RESIZE_MAX_DIM}, got {N} images -> "
+                         f"{H2} x {W2}")
+    geom, totals = _jpeg.mixed_layout(sizes)
+    _jpeg.check_shrink(sizes, (H2, W2), "resize_u8_mixed")
+    if packed.numel() < totals[2]:
+        raise ValueError(f"resize_u8_mixed: the packed buffer has {packed.numel()} bytes, the images need {totals[2]}")
+    if not packed.is_contiguous():
+        raise ValueError("openibl_amd: tensors must be contiguous")
+    dev = _need_cuda(packed)
+    return _resize_u8_mixed(packed, torch.from_numpy(geom).to(dev, non_blocking=True), sizes, H2, W2, out, mean, std,
+                            dev)
+
+
+def _resize_u8_mixed(packed, geom_dev, sizes, H2, W2, out, mean, std, dev):
+    lib = _lib.load()
+    N = sizes.shape[0]
+    if out == "uint8":
+        res = torch.empty((N, H2, W2, 3), dtype=torch.uint8, device=dev)
+    else:
+        res = torch.empty((N, 3, H2, W2), dtype=torch.float32, device=dev)
+    sp = sizes.ctypes.data_as(C.c_void_p)
+    ws = workspace(lib.oibl_resize_u8_mixed_workspace_bytes(sp, N, H2, W2), dev, slot="resize_u8")
+    m3 = (C.c_float * 3)(*[float(v) for v in mean])
+    s3 = (C.c_float * 3)(*[float(v) for v in std])
+    _lib.check(lib.oibl_resize_u8_mixed(_ptr(packed), packed.numel(), _ptr(geom_dev), sp, N, H2, W2, JITTER_OUT[out],
+                                        m3, s3, _ptr(res), _ptr(ws), ws.numel(), _stream(dev)), "resize_u8_mixed")
+    return res
+
+
+def decode_resize_jpeg(batch, size, out: str = "uint8", check: bool = True, scan: str = "auto", chunk_bytes=None,
+                       mean=REF_MEAN, std=REF_STD):
+    """From files to the dense batch the model reads, in two device calls: decode a `jpeg.MixedJpegBatch` (any mix of
+    stored sizes) into the packed buffer and resize every image to size = (height, width) — [N][height][width][3]
+    uint8, or with out='float' [N][3][height][width] float32 normalised.  Every image has the bytes of
+    `Image.open(f).convert('RGB').resize((width, height), Image.BILINEAR)`.  A plain `jpeg.JpegBatch` takes the
+    uniform calls, `resize_u8(decode_jpeg(batch))`.  check=False returns (batch, status) without a sync."""
+    from . import jpeg as _jpeg
+    if not isinstance(size, (tuple, list)) or len(size) != 2:
+        raise ValueError(f"decode_resize_jpeg: size must be (height, width), got {size!r}")
+    if out not in JITTER_OUT:
+        raise ValueError(f"decode_resize_jpeg: out must be 'float' or 'uint8', not {out!r}")
+    if isinstance(batch, _jpeg.JpegBatch):
+        pixels, status = decode_jpeg(batch, check=False, scan=scan, chunk_bytes=chunk_bytes)
+        res = resize_u8(pixels, size, out=out, mean=mean, std=std)
+    else:
+        if not isinstance(batch, _jpeg.MixedJpegBatch):
+            raise ValueError(f"decode_resize_jpeg expects a MixedJpegBatch or a JpegBatch (openibl_amd.jpeg."
+                             f"collate_mixed / collate), got {type(batch).__name__}")
+        H2, W2 = int(size[0]), int(size[1])
+        sizes = _mixed_sizes(batch.sizes, "decode_resize_jpeg")
+        if H2 > RESIZE_MAX_DIM or W2 > RESIZE_MAX_DIM:
+            raise ValueError(f"decode_resize_jpeg: every size <= {RESIZE_MAX_DIM}, got -> {H2} x {W2}")
+        _jpeg.check_shrink(sizes, (H2, W2), "decode_resize_jpeg")
+        packed, status = _decode_jpeg_mixed_packed(batch, scan, chunk_bytes)
+        res = _resize_u8_mixed(packed, batch.geom, sizes, H2, W2, out, mean, std, packed.device)
+    if not check:
+        return res, status
+    _raise_damaged("decode_resize_jpeg", status)
+    return res

@@ -91,9 +91,11 @@ class TrunkCache:
         max_bytes: refuse (ValueError) a cache above it; default a quarter of the device's free memory now.
         input_resize: as in `extract_features` — the loader's raw uint8 batches are resized on the device first.
         input_decode: as in `extract_features` — the loader's JpegBatch batches are decoded on the device in front of
-        that; RuntimeError lists the damaged files when the loader has ended."""
+        that; RuntimeError lists the damaged files when the loader has ended.  MixedJpegBatch batches (files of mixed
+        stored sizes, `jpeg.collate_mixed`) need input_resize=(height, width) and are decoded and resized in one step."""
         from .evaluators import _rank_world
-        from .extract import _batch_names, apply_input_decode, apply_input_resize, check_input_decode, input_resizer
+        from .extract import (_batch_names, apply_input_decode, apply_input_resize, check_input_decode, input_resizer,
+                              is_mixed_batch)
         from .jpeg import scan_route
         resize = input_resizer(input_resize)
         decoded = []
@@ -122,11 +124,13 @@ class TrunkCache:
         with torch.no_grad():
             for batch in loader:
                 imgs = batch[0]
+                mixed = bool(input_decode) and is_mixed_batch(imgs)
                 if input_decode:
-                    imgs = apply_input_decode(imgs, dev, decoded, _batch_names(batch), scan=scan_route(input_decode))
+                    imgs = apply_input_decode(imgs, dev, decoded, _batch_names(batch), scan=scan_route(input_decode),
+                                              resize=resize)
                 if not torch.is_tensor(imgs):
                     imgs = torch.as_tensor(imgs)
-                if resize is not None:
+                if resize is not None and not mixed:
                     imgs = apply_input_resize(resize, imgs, dev)
                 if imgs.dtype != torch.uint8 and imgs.dtype != torch.float32:
                     imgs = imgs.float()
