@@ -823,7 +823,7 @@ int oibl_jpeg_decode(const uint8_t* scan_bytes, size_t scan_len, const void* rec
                      size_t ws_bytes, void* stream);
 
 /* The same decoder with many lanes inside one segment, for scans without restart markers, where oibl_jpeg_decode has
- * one lane per image (csrc/jpeg_chunked.hip and csrc/jpeg_chunked.h state the method: self-synchronising Huffman
+ * one lane per image (csrc/jpeg.hip and csrc/jpeg_chunked.h state the method: self-synchronising Huffman
  * decoding).  Arguments, record, segment table, output and status are those of oibl_jpeg_decode, and so are the bits.
  * Every segment is cut into chunks of chunk_bytes raw bytes (4 <= chunk_bytes <= 65536); one workgroup serves a
  * segment with a lane per chunk, at most 1024 — the last lane takes what is left.  The lanes decode their chunks from

@@ -1,5 +1,5 @@
 // Parallel entropy decoding inside one segment (a restart-free scan, or a long restart interval) by self-synchronising
-// Huffman decoding: the chunk state machine of csrc/jpeg_chunked.hip on top of jpeg_entropy.h.  Like that file it is
+// Huffman decoding: the chunk state machine of csrc/jpeg.hip on top         of jpeg_entropy.h.  Like that file it is
 // compiled into the kernel and, without hipcc, into a host program (tests/helpers/jpeg_chunked_harness.cpp).
 //
 // A segment bytes[begin, end) is cut into chunks of `chunk_bytes` raw bytes, one lane each.  The decoder's state at a

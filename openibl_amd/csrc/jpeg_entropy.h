@@ -242,3 +242,20 @@ JPEG_HD static inline int jpeg_decode_segment(const uint8_t* bytes, uint32_t beg
     return JPEG_ST_BAD_RESTART;
   return JPEG_ST_OK;
 }
+
+// Segment k of the image with geometry g as the serial route decodes it: row g.seg_first + k of the batch's segment
+// table segs[S][2], clamped at 0, the MCUs of restart interval k (all of them without restarts) and the marker that
+// must follow.  Returns the segment's status; JPEG_ST_OK, with nothing read or written, for a k the image or the
+// table does not have.
+JPEG_HD static inline int jpeg_serial_segment(const uint8_t* bytes, uint32_t total_bytes, const JpegGeom& g,
+                                              const int32_t* segs, int S, const JpegHuff* huff, const uint8_t* zz,
+                                              int k, int16_t* coef_image) {
+  if (k >= g.nseg || g.seg_first > S - 1 - k) return JPEG_ST_OK;
+  const int sidx = g.seg_first + k;
+  const int total = g.mcus_x * g.mcus_y;
+  const int want = jpeg_segments_wanted(total, g.dri);
+  const int32_t sb = segs[2 * sidx], se = segs[2 * sidx + 1];
+  const uint32_t begin = sb > 0 ? (uint32_t)sb : 0u, end = se > 0 ? (uint32_t)se : 0u;
+  return jpeg_decode_segment(bytes, begin, end, total_bytes, g, huff, zz, g.dri ? k * g.dri : 0,
+                             g.dri ? g.dri : total, (g.dri && k + 1 < want) ? (k & 7) : -1, coef_image);
+}

@@ -1,4 +1,4 @@
-// The per-image geometry table of csrc/jpeg_mixed.hip: a batch of JPEG files of MIXED stored sizes.  Like
+// The per-image geometry table of csrc/jpeg.hip: a batch of JPEG files of MIXED stored sizes.  Like
 // jpeg_entropy.h this text is compiled into the library and, without hipcc, into a host program
 // (tests/helpers/jpeg_mixed_harness.cpp): nothing here needs a HIP header.
 //

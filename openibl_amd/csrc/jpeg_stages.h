@@ -1,8 +1,7 @@
 // The device text the JPEG decoders share behind the parser: what one lane, one thread or one workgroup does in each
-// stage, written once.  csrc/jpeg.hip (a batch of one stored size: H, W and the image's slices follow from kernel
-// arguments and the image index) and csrc/jpeg_mixed.hip (every image its own size: they come from a per-image
-// geometry table) wrap these bodies in kernels that differ only in where an image's H, W and base pointers come from;
-// csrc/jpeg_chunked.hip uses the chunked entropy stage.  jpeg.hip's header comment says what the stages do.
+// stage, written once.  csrc/jpeg.hip wraps these bodies in two families of kernels that differ only in where an
+// image's H, W and base pointers come from: for a batch of one stored size from kernel arguments and the image index,
+// for a batch of mixed sizes from a per-image geometry table.  Its header comment says what the stages do.
 #pragma once
 
 #include "common.h"
@@ -20,17 +19,11 @@ constexpr int JSCAN_MAX_LANES = 1024;
 JPEG_DEV void jpeg_entropy_lane(const uint8_t* bytes, uint32_t total_bytes, const JpegGeom& g, const int32_t* segs,
                                 int S, const JpegHuff* s_huff, const uint8_t* s_zz, int k, int16_t* coef_image,
                                 int32_t* seg_status) {
-  if (k >= g.nseg || g.seg_first > S - 1 - k) return;
-  const int sidx = g.seg_first + k;
-  const int total = g.mcus_x * g.mcus_y;
-  const int want = jpeg_segments_wanted(total, g.dri);
-  const int32_t sb = segs[2 * sidx], se = segs[2 * sidx + 1];
-  const uint32_t begin = sb > 0 ? (uint32_t)sb : 0u, end = se > 0 ? (uint32_t)se : 0u;
-  seg_status[sidx] = jpeg_decode_segment(bytes, begin, end, total_bytes, g, s_huff, s_zz, g.dri ? k * g.dri : 0,
-                                         g.dri ? g.dri : total, (g.dri && k + 1 < want) ? (k & 7) : -1, coef_image);
+  if (k >= g.nseg || g.seg_first > S - 1 - k) return;   // no such segment, no slot for its status
+  seg_status[g.seg_first + k] = jpeg_serial_segment(bytes, total_bytes, g, segs, S, s_huff, s_zz, k, coef_image);
 }
 
-// ---- entropy, one workgroup per segment (the schedule csrc/jpeg_chunked.hip describes) ------------------------------
+// ---- entropy, one workgroup per segment (the schedule csrc/jpeg.hip describes) --------------------------------------
 // Every thread of the workgroup calls it with the same k < g.nseg (g.seg_first <= S - 1 - k); T = blockDim.x, a power
 // of two in [64, JSCAN_MAX_LANES].  s_huff and s_zz are built and a barrier lies behind them.
 JPEG_DEV void jpeg_chunked_segment(const uint8_t* bytes, uint32_t total_bytes, const JpegGeom& g,

@@ -30,7 +30,7 @@ MAX_DIM, MIN_WIDTH = 32768, 8
 ST_OK, ST_BAD_CODE, ST_OVERRUN, ST_OUT_OF_BYTES, ST_BAD_RESTART, ST_BAD_GEOM = range(6)
 STATUS_TEXT = ("ok", "bad Huffman code", "coefficient index above 63", "ran out of bytes",
                "restart marker missing or wrong", "geometry table inconsistent")
-# The chunked route of `ops.decode_jpeg` (csrc/jpeg_chunked.hip): many lanes inside one segment.  scan="auto" takes it
+# The chunked route of `ops.decode_jpeg` (csrc/jpeg_chunked.h): many lanes inside one segment.  scan="auto" takes it
 # when the batch's longest segment has at least CHUNKED_MIN_BYTES bytes; a lane's chunk has CHUNK_BYTES raw bytes, more
 # where a segment would otherwise have more than MAX_CHUNK_LANES chunks.  Both are set from one run on an MI355X
 # (profiles/jpeg_chunked_bench.txt, files of 480 x 640): wherever the chunked route wins, 64-byte chunks were as fast as
@@ -248,41 +248,23 @@ def decode_on_host(data) -> np.ndarray:
         return np.asarray(im.convert("RGB"))
 
 
-class JpegBatch:
-    """N stored images of one size H x W on their way to `ops.decode_jpeg`.  Those the device decodes (at the batch
-    positions `dev_index`) travel as `scan` (uint8, their scans back to back), `records` (uint8 [Nd][REC_BYTES]) and
-    `segments` (int32 [S][2], offsets into `scan`); the others (`host_index`) were decoded on the host and travel as
-    `host_pixels` (uint8 [Nh][H][W][3]).  `reasons[i]` says why image i was decoded on the host ("" otherwise).
-    `max_segment_bytes`: the longest segment, which chooses the route of `ops.decode_jpeg(scan="auto")`."""
+def plane_blocks(H, W):
+    """8 x 8 blocks of one component plane of an H x W image in the decoder's workspace, padded to whole 16 x 16 MCUs
+    (jpeg_blocks_across of csrc/jpeg_entropy.h per axis); ints or numpy arrays."""
+    return (2 * ((W + 15) // 16)) * (2 * ((H + 15) // 16))
 
-    def __init__(self, n, height, width, scan, records, segments, max_segments, dev_index, host_index, host_pixels,
-                 reasons, max_segment_bytes=0):
-        self.n, self.height, self.width = int(n), int(height), int(width)
-        self.scan, self.records, self.segments = scan, records, segments
-        self.max_segments = int(max_segments)
-        self.max_segment_bytes = int(max_segment_bytes)
-        self.dev_index, self.host_index, self.host_pixels = dev_index, host_index, host_pixels
-        self.reasons = tuple(reasons)
 
-    _TENSORS = ("scan", "records", "segments", "dev_index", "host_index", "host_pixels")
+class _Batch:
+    """What JpegBatch and MixedJpegBatch share: N images and the tensors `_TENSORS` names, moved and pinned together.
+    A copy is made through `type(self)` without calling `__init__`, so a subclass keeps its own constructor."""
+
+    _TENSORS = ()
 
     def __len__(self):
         return self.n
 
-    @property
-    def shape(self):
-        return (self.n, self.height, self.width, 3)
-
-    @property
-    def is_cuda(self):
-        return self.scan.is_cuda or self.host_pixels.is_cuda
-
-    @property
-    def device(self):
-        return self.scan.device
-
     def _map(self, fn):
-        out = JpegBatch.__new__(JpegBatch)
+        out = type(self).__new__(type(self))
         out.__dict__.update(self.__dict__)
         for name in self._TENSORS:
             setattr(out, name, fn(getattr(self, name)))
@@ -302,46 +284,99 @@ class JpegBatch:
     def is_pinned(self):
         return all(getattr(self, name).is_pinned() for name in self._TENSORS if getattr(self, name).numel())
 
+
+class _Files(NamedTuple):
+    """What `_walk_files` gathers from the files of a batch."""
+    scan: torch.Tensor          # uint8, the device-decoded images' scans back to back
+    records: torch.Tensor       # uint8 [Nd][REC_BYTES], header word 13 patched to the image's first segment
+    segments: torch.Tensor      # int32 [S][2], offsets into `scan`
+    max_segments: int
+    max_segment_bytes: int
+    dev_index: torch.Tensor     # int64: batch positions of the device-decoded images
+    host_index: torch.Tensor    # int64: of the host-decoded ones
+    host_pixels: list           # numpy uint8 [H][W][3] per host-decoded image
+    reasons: list
+    sizes: list                 # (H, W) per image
+
+
+def _walk_files(files, what) -> _Files:
+    """Parse the files of a batch (bytes, numpy or 1-D uint8 tensors) for the batch class named `what`: the device's
+    share packed, the others decoded on the host."""
+    files = list(files)
+    if not files:
+        raise ValueError(f"{what}: an empty batch")
+    scans, recs, segs, dev_idx, host_idx, host_px, reasons, sizes = [], [], [], [], [], [], [], []
+    at = nseg = max_seg = max_bytes = 0
+    for i, f in enumerate(files):
+        p = parse(f)
+        reasons.append(p.reason)
+        if p.device:
+            if at + p.scan.size >= 1 << 31:
+                raise ValueError(f"{what}: more than 2^31 scan bytes in one batch (at image {i})")
+            rec, sg = p.record.copy(), p.segments + np.int32(at)
+            rec[:64].view(np.int32)[13] = nseg
+            scans.append(p.scan), recs.append(rec), segs.append(sg), dev_idx.append(i)
+            at, nseg, max_seg = at + p.scan.size, nseg + sg.shape[0], max(max_seg, sg.shape[0])
+            max_bytes = max(max_bytes, int((sg[:, 1] - sg[:, 0]).max()))
+            sizes.append((p.height, p.width))
+        else:
+            px = np.ascontiguousarray(decode_on_host(f))
+            host_idx.append(i), host_px.append(px)
+            sizes.append(px.shape[:2])
+    t = torch.from_numpy
+    return _Files(t(np.concatenate(scans)) if scans else torch.empty(0, dtype=torch.uint8),
+                  t(np.stack(recs)) if recs else torch.empty((0, REC_BYTES), dtype=torch.uint8),
+                  t(np.concatenate(segs)) if segs else torch.empty((0, 2), dtype=torch.int32),
+                  max_seg, max_bytes, torch.tensor(dev_idx, dtype=torch.int64),
+                  torch.tensor(host_idx, dtype=torch.int64), host_px, reasons, sizes)
+
+
+class JpegBatch(_Batch):
+    """N stored images of one size H x W on their way to `ops.decode_jpeg`.  Those the device decodes (at the batch
+    positions `dev_index`) travel as `scan` (uint8, their scans back to back), `records` (uint8 [Nd][REC_BYTES]) and
+    `segments` (int32 [S][2], offsets into `scan`); the others (`host_index`) were decoded on the host and travel as
+    `host_pixels` (uint8 [Nh][H][W][3]).  `reasons[i]` says why image i was decoded on the host ("" otherwise).
+    `max_segment_bytes`: the longest segment, which chooses the route of `ops.decode_jpeg(scan="auto")`."""
+
+    def __init__(self, n, height, width, scan, records, segments, max_segments, dev_index, host_index, host_pixels,
+                 reasons, max_segment_bytes=0):
+        self.n, self.height, self.width = int(n), int(height), int(width)
+        self.scan, self.records, self.segments = scan, records, segments
+        self.max_segments = int(max_segments)
+        self.max_segment_bytes = int(max_segment_bytes)
+        self.dev_index, self.host_index, self.host_pixels = dev_index, host_index, host_pixels
+        self.reasons = tuple(reasons)
+
+    _TENSORS = ("scan", "records", "segments", "dev_index", "host_index", "host_pixels")
+
+    @property
+    def shape(self):
+        return (self.n, self.height, self.width, 3)
+
+    @property
+    def is_cuda(self):
+        return self.scan.is_cuda or self.host_pixels.is_cuda
+
+    @property
+    def device(self):
+        return self.scan.device
+
     @classmethod
     def from_files(cls, files) -> "JpegBatch":
         """files: the bytes of N files (bytes, numpy or 1-D uint8 tensors) of one stored size; ValueError for a mix of
         sizes (a batch of one is always fine)."""
-        files = list(files)
-        if not files:
-            raise ValueError("JpegBatch: an empty batch")
-        scans, recs, segs, dev_idx, host_idx, host_px, reasons, sizes = [], [], [], [], [], [], [], []
-        at = nseg = max_seg = max_bytes = 0
-        for i, f in enumerate(files):
-            p = parse(f)
-            reasons.append(p.reason)
-            if p.device:
-                if at + p.scan.size >= 1 << 31:
-                    raise ValueError(f"JpegBatch: more than 2^31 scan bytes in one batch (at image {i})")
-                rec, sg = p.record.copy(), p.segments + np.int32(at)
-                rec[:64].view(np.int32)[13] = nseg
-                scans.append(p.scan), recs.append(rec), segs.append(sg), dev_idx.append(i)
-                at, nseg, max_seg = at + p.scan.size, nseg + sg.shape[0], max(max_seg, sg.shape[0])
-                max_bytes = max(max_bytes, int((sg[:, 1] - sg[:, 0]).max()))
-                sizes.append((p.height, p.width))
-            else:
-                px = decode_on_host(f)
-                host_idx.append(i), host_px.append(px)
-                sizes.append(px.shape[:2])
-        if len(set(sizes)) != 1:
-            raise ValueError(f"JpegBatch: images of mixed stored sizes {sorted(set(sizes))} in one batch (use a batch "
-                             f"size of 1 or a loader that groups them)")
-        H, W = sizes[0]
-        t = torch.from_numpy
-        return cls(len(files), H, W,
-                   t(np.concatenate(scans)) if scans else torch.empty(0, dtype=torch.uint8),
-                   t(np.stack(recs)) if recs else torch.empty((0, REC_BYTES), dtype=torch.uint8),
-                   t(np.concatenate(segs)) if segs else torch.empty((0, 2), dtype=torch.int32),
-                   max_seg, torch.tensor(dev_idx, dtype=torch.int64), torch.tensor(host_idx, dtype=torch.int64),
-                   t(np.stack(host_px)) if host_px else torch.empty((0, H, W, 3), dtype=torch.uint8), reasons,
-                   max_bytes)
+        f = _walk_files(files, "JpegBatch")
+        if len(set(f.sizes)) != 1:
+            raise ValueError(f"JpegBatch: images of mixed stored sizes {sorted(set(f.sizes))} in one batch (use a "
+                             f"batch size of 1 or a loader that groups them)")
+        H, W = f.sizes[0]
+        host_pixels = torch.from_numpy(np.stack(f.host_pixels)) if f.host_pixels else \
+            torch.empty((0, H, W, 3), dtype=torch.uint8)
+        return cls(len(f.sizes), H, W, f.scan, f.records, f.segments, f.max_segments, f.dev_index, f.host_index,
+                   host_pixels, f.reasons, f.max_segment_bytes)
 
 
-# ---- batches of mixed stored sizes (csrc/jpeg_mixed.h, csrc/jpeg_mixed.hip) ------------------------------------------
+# ---- batches of mixed stored sizes (csrc/jpeg_mixed.h, csrc/jpeg.hip) ------------------------------------------------
 GEOM_INTS = 8                 # JPEG_MIX_GEOM_INTS: H, W, coefficient base, plane base, pixel offset low / high, 0, 0
 PIX_ALIGN = 64                # JPEG_MIX_PIX_ALIGN: every image of the packed pixels starts on a multiple of it
 MAX_SHRINK = 16               # RS_MAX_SCALE of csrc/resize_tables.h: the largest stored / target size per axis
@@ -362,7 +397,7 @@ def mixed_layout(sizes):
         raise ValueError(f"mixed_layout: image {i} is {sizes[i, 0]} x {sizes[i, 1]}, every side must be in "
                          f"[1, {MAX_DIM}]")
     H, W = sizes[:, 0], sizes[:, 1]
-    bb = (2 * ((W + 15) // 16)) * (2 * ((H + 15) // 16))
+    bb = plane_blocks(H, W)
     blocks = np.concatenate([[0], np.cumsum(3 * bb)])
     if blocks[-1] >= 1 << 31:
         raise ValueError(f"mixed_layout: 2^31 coefficient blocks or more at image "
@@ -398,7 +433,7 @@ def check_shrink(sizes, target, what="MixedJpegBatch") -> None:
                              f"the limit of {MAX_SHRINK}")
 
 
-class MixedJpegBatch:
+class MixedJpegBatch(_Batch):
     """N stored images of ANY sizes on their way to `ops.decode_resize_jpeg` / `ops.decode_jpeg_mixed`.  As in a
     JpegBatch the images the device decodes (batch positions `dev_index`) travel as `scan`, `records` and `segments`,
     the others (`host_index`; `reasons[i]` says why) as pixels decoded on the host: `host_pixels`, ONE packed uint8
@@ -427,9 +462,6 @@ class MixedJpegBatch:
         self.host_pixels, self.host_offsets = host_pixels, tuple(int(v) for v in host_offsets)
         self.reasons = tuple(reasons)
 
-    def __len__(self):
-        return self.n
-
     @property
     def is_cuda(self):
         return self.geom.is_cuda
@@ -443,27 +475,6 @@ class MixedJpegBatch:
         """Do all images have one stored size?"""
         return bool((self.sizes == self.sizes[0]).all())
 
-    def _map(self, fn):
-        out = MixedJpegBatch.__new__(MixedJpegBatch)
-        out.__dict__.update(self.__dict__)
-        for name in self._TENSORS:
-            setattr(out, name, fn(getattr(self, name)))
-        return out
-
-    def to(self, device, non_blocking=False):
-        return self._map(lambda t: t.to(device, non_blocking=non_blocking))
-
-    def cuda(self, device=None, non_blocking=False):
-        dev = torch.device("cuda", torch.cuda.current_device() if device is None else device) \
-            if not isinstance(device, torch.device) else device
-        return self.to(dev, non_blocking=non_blocking)
-
-    def pin_memory(self):
-        return self._map(lambda t: t.pin_memory() if t.numel() else t)
-
-    def is_pinned(self):
-        return all(getattr(self, name).is_pinned() for name in self._TENSORS if getattr(self, name).numel())
-
     @classmethod
     def from_files(cls, files, target=None) -> "MixedJpegBatch":
         """files: the bytes of N files (bytes, numpy or 1-D uint8 tensors) of any stored sizes.  target = (h, w): the
@@ -471,31 +482,12 @@ class MixedJpegBatch:
         here, in the loader's worker (without it the device call raises).  A file with a side above MAX_DIM = 32768
         — only a host-decoded one can have it, a PNG for instance — is a ValueError as well: neither the layout nor
         the resize takes it, as `ops.resize_u8` does not."""
-        files = list(files)
-        if not files:
-            raise ValueError("MixedJpegBatch: an empty batch")
-        scans, recs, segs, dev_idx, host_idx, host_px, reasons, sizes = [], [], [], [], [], [], [], []
-        at = nseg = max_seg = max_bytes = 0
-        for i, f in enumerate(files):
-            p = parse(f)
-            reasons.append(p.reason)
-            if p.device:
-                if at + p.scan.size >= 1 << 31:
-                    raise ValueError(f"MixedJpegBatch: more than 2^31 scan bytes in one batch (at image {i})")
-                rec, sg = p.record.copy(), p.segments + np.int32(at)
-                rec[:64].view(np.int32)[13] = nseg
-                scans.append(p.scan), recs.append(rec), segs.append(sg), dev_idx.append(i)
-                at, nseg, max_seg = at + p.scan.size, nseg + sg.shape[0], max(max_seg, sg.shape[0])
-                max_bytes = max(max_bytes, int((sg[:, 1] - sg[:, 0]).max()))
-                sizes.append((p.height, p.width))
-            else:
-                px = np.ascontiguousarray(decode_on_host(f))
-                host_idx.append(i), host_px.append(px.reshape(-1))
-                sizes.append(px.shape[:2])
-        sizes = np.asarray(sizes, np.int32).reshape(-1, 2)
+        f = _walk_files(files, "MixedJpegBatch")
+        sizes = np.asarray(f.sizes, np.int32).reshape(-1, 2)
         if target is not None:
             check_shrink(sizes, target)
         geom, totals = mixed_layout(sizes)
+        dev_idx = f.dev_index.tolist()
         if dev_idx:
             dev_geom, dev_totals = mixed_layout(sizes[dev_idx])
             dev_geom[:, 4:6] = geom[dev_idx, 4:6]
@@ -503,13 +495,12 @@ class MixedJpegBatch:
         else:
             dev_geom, dev_totals = np.zeros((0, GEOM_INTS), np.int32), (0, 0, totals[2], 0, 0, 0)
         t = torch.from_numpy
-        return cls(len(files), t(sizes), t(geom), totals, t(dev_geom), dev_totals,
-                   t(np.concatenate(scans)) if scans else torch.empty(0, dtype=torch.uint8),
-                   t(np.stack(recs)) if recs else torch.empty((0, REC_BYTES), dtype=torch.uint8),
-                   t(np.concatenate(segs)) if segs else torch.empty((0, 2), dtype=torch.int32),
-                   max_seg, torch.tensor(dev_idx, dtype=torch.int64), torch.tensor(host_idx, dtype=torch.int64),
+        host_px = [px.reshape(-1) for px in f.host_pixels]
+        return cls(len(sizes), t(sizes), t(geom), totals, t(dev_geom), dev_totals, f.scan, f.records, f.segments,
+                   f.max_segments, f.dev_index, f.host_index,
                    t(np.concatenate(host_px)) if host_px else torch.empty(0, dtype=torch.uint8),
-                   np.concatenate([[0], np.cumsum([p.size for p in host_px])]).astype(np.int64), reasons, max_bytes)
+                   np.concatenate([[0], np.cumsum([p.size for p in host_px])]).astype(np.int64), f.reasons,
+                   f.max_segment_bytes)
 
 
 def scan_route(input_decode) -> str:
@@ -522,24 +513,23 @@ def scan_route(input_decode) -> str:
     raise ValueError(f"input_decode must be True or one of {SCAN_ROUTES}, not {input_decode!r}")
 
 
-def collate(items):
-    """DataLoader `collate_fn` for a dataset whose item 0 is a file's bytes (`Preprocessor(..., raw=True)`): item 0 of
-    the batch is a JpegBatch, the other fields are collated as usual."""
+def _collate(items, make):
     from torch.utils.data import default_collate
     first = items[0]
     if torch.is_tensor(first) or isinstance(first, (bytes, bytearray, np.ndarray)):
-        return JpegBatch.from_files(items)
+        return make(items)
     rest = default_collate([tuple(it[1:]) for it in items]) if len(first) > 1 else []
-    return [JpegBatch.from_files([it[0] for it in items])] + list(rest)
+    return [make([it[0] for it in items])] + list(rest)
+
+
+def collate(items):
+    """DataLoader `collate_fn` for a dataset whose item 0 is a file's bytes (`Preprocessor(..., raw=True)`): item 0 of
+    the batch is a JpegBatch, the other fields are collated as usual."""
+    return _collate(items, JpegBatch.from_files)
 
 
 def collate_mixed(items, target=None):
     """`collate` for files of mixed stored sizes: item 0 of the batch is a MixedJpegBatch, the other fields are
     collated as usual.  target = (h, w), the size of the resize behind the decoder, makes an image beyond the resize's
     shrink limit a ValueError in the worker: `collate_fn=functools.partial(jpeg.collate_mixed, target=(480, 640))`."""
-    from torch.utils.data import default_collate
-    first = items[0]
-    if torch.is_tensor(first) or isinstance(first, (bytes, bytearray, np.ndarray)):
-        return MixedJpegBatch.from_files(items, target=target)
-    rest = default_collate([tuple(it[1:]) for it in items]) if len(first) > 1 else []
-    return [MixedJpegBatch.from_files([it[0] for it in items], target=target)] + list(rest)
+    return _collate(items, lambda files: MixedJpegBatch.from_files(files, target=target))

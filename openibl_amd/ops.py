@@ -2046,6 +2046,15 @@ def resize_u8_tables(in_size: int, out_size: int, device=None) -> Tuple[torch.Te
     return bounds, coeff
 
 
+def _resize_result(N, H2, W2, out, mean, std, dev):
+    """What the two uint8 resizes hand their C calls alike: the result for out = 'uint8' or 'float', mean and std."""
+    if out == "uint8":
+        res = torch.empty((N, H2, W2, 3), dtype=torch.uint8, device=dev)
+    else:
+        res = torch.empty((N, 3, H2, W2), dtype=torch.float32, device=dev)
+    return res, (C.c_float * 3)(*[float(v) for v in mean]), (C.c_float * 3)(*[float(v) for v in std])
+
+
 def resize_u8(u8: torch.Tensor, size, out: str = "uint8", mean=REF_MEAN, std=REF_STD) -> torch.Tensor:
     """Bilinear resize of a raw batch on the device (oibl_resize_u8), PIL's bits: u8 [N][H][W][3] uint8,
     size = (height, width) of the result.  It is `Image.resize((width, height), Image.BILINEAR)` of every image —
@@ -2075,13 +2084,8 @@ def resize_u8(u8: torch.Tensor, size, out: str = "uint8", mean=REF_MEAN, std=REF
         raise ValueError("openibl_amd: tensors must be contiguous")
     dev = _need_cuda(u8)
     lib = _lib.load()
-    if out == "uint8":
-        res = torch.empty((N, H2, W2, 3), dtype=torch.uint8, device=dev)
-    else:
-        res = torch.empty((N, 3, H2, W2), dtype=torch.float32, device=dev)
+    res, m3, s3 = _resize_result(N, H2, W2, out, mean, std, dev)
     ws = workspace(lib.oibl_resize_u8_workspace_bytes(N, H, W, H2, W2), dev, slot="resize_u8")
-    m3 = (C.c_float * 3)(*[float(v) for v in mean])
-    s3 = (C.c_float * 3)(*[float(v) for v in std])
     _lib.check(lib.oibl_resize_u8(_ptr(u8), N, H, W, H2, W2, JITTER_OUT[out], m3, s3, _ptr(res), _ptr(ws),
                                   ws.numel(), _stream(dev)), "resize_u8")
     return res
@@ -2109,14 +2113,10 @@ def decode_jpeg(batch, check: bool = True, scan: str = "auto", chunk_bytes=None)
     check=True reads the per-image status back (one host sync) and raises ValueError naming the damaged images;
     check=False returns (pixels, status) without a sync: status int32 [N], 0 ok (`jpeg.STATUS_TEXT`), 0 for the
     host-decoded images."""
-    global last_jpeg_route, last_jpeg_rounds
     from . import jpeg as _jpeg
     if not isinstance(batch, _jpeg.JpegBatch):
         raise ValueError(f"decode_jpeg expects a JpegBatch (openibl_amd.jpeg.collate), got {type(batch).__name__}")
-    if scan not in _jpeg.SCAN_ROUTES:
-        raise ValueError(f"decode_jpeg: scan must be one of {_jpeg.SCAN_ROUTES}, not {scan!r}")
-    if chunk_bytes is not None and not 4 <= int(chunk_bytes) <= 65536:
-        raise ValueError(f"decode_jpeg: chunk_bytes {chunk_bytes} must be in [4, 65536]")
+    route, cb = _jpeg_route("decode_jpeg", batch, scan, chunk_bytes)
     dev = _need_cuda(batch.scan, batch.records, batch.segments, batch.host_pixels, batch.dev_index,
                      batch.host_index)
     N, H, W = batch.n, batch.height, batch.width
@@ -2132,42 +2132,67 @@ def decode_jpeg(batch, check: bool = True, scan: str = "auto", chunk_bytes=None)
         lib = _lib.load()
         S = int(batch.segments.shape[0])
         pixels = torch.empty((nd, H, W, 3), dtype=torch.uint8, device=dev)
-        st = status if nh == 0 else torch.empty(nd, dtype=torch.int32, device=dev)
-        if scan == "auto":
-            scan = "chunked" if batch.max_segment_bytes >= _jpeg.CHUNKED_MIN_BYTES else "serial"
-        if scan == "chunked":
-            cb = int(chunk_bytes) if chunk_bytes is not None else \
-                min(65536, max(_jpeg.CHUNK_BYTES, -(-batch.max_segment_bytes // _jpeg.MAX_CHUNK_LANES)))
-            need = lib.oibl_jpeg_decode_chunked_workspace_bytes(nd, H, W, S, cb)
-            ws = workspace(need, dev, slot="jpeg_decode")
-            _lib.check(lib.oibl_jpeg_decode_chunked(_ptr(batch.scan), batch.scan.numel(), _ptr(batch.records),
-                                                    _ptr(batch.segments), S, batch.max_segments, nd, H, W, cb,
-                                                    _ptr(pixels), _ptr(st), _ptr(ws), ws.numel(), _stream(dev)),
-                       "jpeg_decode_chunked")
-            # the workspace: int16 coef[nd][3][Bh][Bw][64], int32 segment status [S], int32 rounds [S], the planes
-            at = _align256(nd * 3 * (2 * ((H + 15) // 16)) * (2 * ((W + 15) // 16)) * 64 * 2) + _align256(4 * S)
-            last_jpeg_rounds = ws[at:at + 4 * S].view(torch.int32)
+        coef_bytes = nd * 3 * _jpeg.plane_blocks(H, W) * 64 * 2     # int16 coef[nd][3][Bh][Bw][64]
+        if cb:
+            _jpeg_launch(batch, pixels, status, route, coef_bytes,
+                         lib.oibl_jpeg_decode_chunked_workspace_bytes(nd, H, W, S, cb), lib.oibl_jpeg_decode_chunked,
+                         "jpeg_decode_chunked", (H, W, cb))
         else:
-            ws = workspace(lib.oibl_jpeg_decode_workspace_bytes(nd, H, W, S), dev, slot="jpeg_decode")
-            _lib.check(lib.oibl_jpeg_decode(_ptr(batch.scan), batch.scan.numel(), _ptr(batch.records),
-                                            _ptr(batch.segments), S, batch.max_segments, nd, H, W, _ptr(pixels),
-                                            _ptr(st), _ptr(ws), ws.numel(), _stream(dev)), "jpeg_decode")
-            last_jpeg_rounds = None
-        last_jpeg_route = scan
+            _jpeg_launch(batch, pixels, status, route, coef_bytes, lib.oibl_jpeg_decode_workspace_bytes(nd, H, W, S),
+                         lib.oibl_jpeg_decode, "jpeg_decode", (H, W))
     if nh:
         out = torch.empty((N, H, W, 3), dtype=torch.uint8, device=dev)
         out[batch.host_index] = batch.host_pixels
         if nd:
             out[batch.dev_index] = pixels
-            status[batch.dev_index] = st
         pixels = out
     if not check:
         return pixels, status
-    bad = status.cpu().numpy()
-    if bad.any():
-        raise ValueError("decode_jpeg: damaged JPEG streams: " + ", ".join(
-            f"image {i} ({_jpeg.STATUS_TEXT[min(int(s), 4)]})" for i, s in enumerate(bad) if s))
+    _raise_damaged("decode_jpeg", status)
     return pixels
+
+
+def _jpeg_route(what, batch, scan, chunk_bytes):
+    """(route, chunk_bytes) of a decode call: route "serial" or "chunked" — "auto" looks at the batch's longest
+    segment — and the bytes of a lane's chunk, 0 on the serial route."""
+    from . import jpeg as _jpeg
+    if scan not in _jpeg.SCAN_ROUTES:
+        raise ValueError(f"{what}: scan must be one of {_jpeg.SCAN_ROUTES}, not {scan!r}")
+    if chunk_bytes is not None and not 4 <= int(chunk_bytes) <= 65536:
+        raise ValueError(f"{what}: chunk_bytes {chunk_bytes} must be in [4, 65536]")
+    if scan == "auto":
+        scan = "chunked" if batch.max_segment_bytes >= _jpeg.CHUNKED_MIN_BYTES else "serial"
+    if scan != "chunked":
+        return scan, 0
+    if chunk_bytes is not None:
+        return scan, int(chunk_bytes)
+    return scan, min(65536, max(_jpeg.CHUNK_BYTES, -(-batch.max_segment_bytes // _jpeg.MAX_CHUNK_LANES)))
+
+
+def _jpeg_rounds(ws, coef_bytes, S):
+    """The settle rounds of the chunked route, int32 [S], as a view of a decode call's workspace `ws` (uint8).  The
+    only place in Python that knows the workspace of csrc/jpeg.hip (jpeg_layout): the coefficients, int32 segment
+    status [S], int32 rounds [S], the planes, each region on a multiple of 256 bytes
+    (tests/test_jpeg_chunked_cpu.py holds it to the C workspace queries)."""
+    at = _align256(coef_bytes) + _align256(4 * S)
+    return ws[at:at + 4 * S].view(torch.int32)
+
+
+def _jpeg_launch(batch, out, status, route, coef_bytes, need, entry, name, geometry):
+    """The device's share of a decode call: `entry` (one of the three C decoders; `geometry` is what it takes between
+    the image count and the output) writes the pixels to `out` and the statuses to the batch positions `dev_index` of
+    `status`; the route and the rounds of the call become `last_jpeg_route` and `last_jpeg_rounds`."""
+    global last_jpeg_route, last_jpeg_rounds
+    dev = status.device
+    nd, S = int(batch.records.shape[0]), int(batch.segments.shape[0])
+    st = status if nd == batch.n else torch.empty(nd, dtype=torch.int32, device=dev)
+    ws = workspace(need, dev, slot="jpeg_decode")
+    _lib.check(entry(_ptr(batch.scan), batch.scan.numel(), _ptr(batch.records), _ptr(batch.segments), S,
+                     batch.max_segments, nd, *geometry, _ptr(out), _ptr(st), _ptr(ws), ws.numel(), _stream(dev)), name)
+    last_jpeg_rounds = _jpeg_rounds(ws, coef_bytes, S) if route == "chunked" else None
+    last_jpeg_route = route
+    if st is not status:
+        status[batch.dev_index] = st
 
 
 # ---------------------------------------------------------------------------------------------
@@ -2189,15 +2214,11 @@ def _totals6(totals):
 def _decode_jpeg_mixed_packed(batch, scan, chunk_bytes):
     """The packed pixel buffer (uint8 [batch.totals[2]]) and the statuses (int32 [N]) of a MixedJpegBatch on the
     device: one decoder call for the device-decoded images, one copy per host-decoded image into its slot."""
-    global last_jpeg_route, last_jpeg_rounds
     from . import jpeg as _jpeg
     if not isinstance(batch, _jpeg.MixedJpegBatch):
         raise ValueError(f"decode_jpeg_mixed expects a MixedJpegBatch (openibl_amd.jpeg.collate_mixed), got "
                          f"{type(batch).__name__}")
-    if scan not in _jpeg.SCAN_ROUTES:
-        raise ValueError(f"decode_jpeg_mixed: scan must be one of {_jpeg.SCAN_ROUTES}, not {scan!r}")
-    if chunk_bytes is not None and not 4 <= int(chunk_bytes) <= 65536:
-        raise ValueError(f"decode_jpeg_mixed: chunk_bytes {chunk_bytes} must be in [4, 65536]")
+    route, cb = _jpeg_route("decode_jpeg_mixed", batch, scan, chunk_bytes)
     dev = _need_cuda(batch.scan, batch.records, batch.segments, batch.host_pixels, batch.dev_index,
                      batch.host_index, batch.geom, batch.dev_geom)
     N = batch.n
@@ -2211,30 +2232,14 @@ def _decode_jpeg_mixed_packed(batch, scan, chunk_bytes):
     if nd:
         lib = _lib.load()
         S = int(batch.segments.shape[0])
-        st = status if nh == 0 else torch.empty(nd, dtype=torch.int32, device=dev)
-        if scan == "auto":
-            scan = "chunked" if batch.max_segment_bytes >= _jpeg.CHUNKED_MIN_BYTES else "serial"
-        cb = 0
-        if scan == "chunked":
-            cb = int(chunk_bytes) if chunk_bytes is not None else \
-                min(65536, max(_jpeg.CHUNK_BYTES, -(-batch.max_segment_bytes // _jpeg.MAX_CHUNK_LANES)))
         totals = _totals6(batch.dev_totals)
         need = lib.oibl_jpeg_decode_mixed_workspace_bytes(totals, nd, S)
         if need == 0:
             raise ValueError(f"decode_jpeg_mixed: {nd} images, {S} segments, totals {batch.dev_totals}: outside the "
                              f"decoder's limits (at most 65535 images of at least {_jpeg.MIN_WIDTH} and at most "
                              f"{_jpeg.MAX_DIM} pixels per side)")
-        ws = workspace(need, dev, slot="jpeg_decode")
-        _lib.check(lib.oibl_jpeg_decode_mixed(_ptr(batch.scan), batch.scan.numel(), _ptr(batch.records),
-                                              _ptr(batch.segments), S, batch.max_segments, nd, _ptr(batch.dev_geom),
-                                              totals, cb, _ptr(packed), _ptr(st), _ptr(ws), ws.numel(),
-                                              _stream(dev)), "jpeg_decode_mixed")
-        # the workspace: the coefficients, int32 segment status [S], int32 rounds [S], the planes
-        at = _align256(batch.dev_totals[0]) + _align256(4 * S)
-        last_jpeg_rounds = ws[at:at + 4 * S].view(torch.int32) if cb else None
-        last_jpeg_route = scan
-        if nh:
-            status[batch.dev_index] = st
+        _jpeg_launch(batch, packed, status, route, batch.dev_totals[0], need, lib.oibl_jpeg_decode_mixed,
+                     "jpeg_decode_mixed", (_ptr(batch.dev_geom), totals, cb))
     if nh:
         offs = _jpeg.geom_pixel_offsets(batch.geom_host)
         sizes = batch.sizes.tolist()
@@ -2316,14 +2321,9 @@ def resize_u8_mixed(packed: torch.Tensor, sizes, size, out: str = "uint8", mean=
 def _resize_u8_mixed(packed, geom_dev, sizes, H2, W2, out, mean, std, dev):
     lib = _lib.load()
     N = sizes.shape[0]
-    if out == "uint8":
-        res = torch.empty((N, H2, W2, 3), dtype=torch.uint8, device=dev)
-    else:
-        res = torch.empty((N, 3, H2, W2), dtype=torch.float32, device=dev)
+    res, m3, s3 = _resize_result(N, H2, W2, out, mean, std, dev)
     sp = sizes.ctypes.data_as(C.c_void_p)
     ws = workspace(lib.oibl_resize_u8_mixed_workspace_bytes(sp, N, H2, W2), dev, slot="resize_u8")
-    m3 = (C.c_float * 3)(*[float(v) for v in mean])
-    s3 = (C.c_float * 3)(*[float(v) for v in std])
     _lib.check(lib.oibl_resize_u8_mixed(_ptr(packed), packed.numel(), _ptr(geom_dev), sp, N, H2, W2, JITTER_OUT[out],
                                         m3, s3, _ptr(res), _ptr(ws), ws.numel(), _stream(dev)), "resize_u8_mixed")
     return res

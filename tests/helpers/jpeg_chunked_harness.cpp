@@ -19,9 +19,9 @@
 #include <vector>
 
 #include "jpeg_chunked.h"
+#include "jpeg_workgroup_emul.h"
 
 static const uint8_t kZigzag[64] = {JPEG_ZIGZAG_LIST};
-static const int kMaxLanes = 1024;   // JSCAN_MAX_LANES
 
 static bool get(FILE* f, void* p, size_t n) { return n == 0 || fread(p, 1, n, f) == n; }
 
@@ -48,63 +48,21 @@ int main(int argc, char** argv) {
     rec32[JPEG_H_SEG_FIRST] = 0;
     rec32[JPEG_H_NSEG] = nseg;
     const JpegGeom g = jpeg_geom(rec32.data(), H, W);
-    const JpegChunkGeom q = jpeg_chunk_geom(g);
     const size_t plane = (size_t)g.Bw * g.Bh * 64;
     int16_t* coef_s = (int16_t*)calloc(3 * plane, sizeof(int16_t));
     int16_t* coef_c = (int16_t*)calloc(3 * plane, sizeof(int16_t));
     JpegHuff* huff = (JpegHuff*)malloc(4 * sizeof(JpegHuff));
     for (int t = 0; t < 4; ++t) jpeg_huff_build(huff + t, rec + JPEG_REC_HUFF + t * JPEG_HUFF_BYTES);
-    // the lane tables: the kernel's s_a .. s_d, the snapshot the barrier makes of s_a / s_b, the lanes' registers
-    JpegChunkState* ent = (JpegChunkState*)malloc(kMaxLanes * sizeof(JpegChunkState));
-    JpegChunkState* ex = (JpegChunkState*)malloc(kMaxLanes * sizeof(JpegChunkState));
-    JpegChunkState* seen = (JpegChunkState*)malloc(kMaxLanes * sizeof(JpegChunkState));
-    JpegChunkSum* sum = (JpegChunkSum*)malloc(kMaxLanes * sizeof(JpegChunkSum));
-    const int total = g.mcus_x * g.mcus_y;
-    const int want = jpeg_segments_wanted(total, g.dri);
     int32_t status_s = 0, status_c = 0;
     std::vector<int32_t> rows;
     for (int k = 0; k < g.nseg; ++k) {
-      const int32_t sb = segs[2 * k], se = segs[2 * k + 1];
-      const int st_s = jpeg_decode_segment(bytes, sb > 0 ? (uint32_t)sb : 0u, se > 0 ? (uint32_t)se : 0u,
-                                           (uint32_t)total_bytes, g, huff, kZigzag, g.dri ? k * g.dri : 0,
-                                           g.dri ? g.dri : total, (g.dri && k + 1 < want) ? (k & 7) : -1, coef_s);
-      // ---- what the workgroup of segment k does ----
-      const JpegChunkSeg sg = jpeg_chunk_segment(g, q, k, sb, se, (uint32_t)total_bytes, chunk_bytes, kMaxLanes);
-      const int L = sg.lanes;
-      std::vector<uint32_t> limit(L);
-      for (int t = 0; t < L; ++t) {
-        const uint32_t start = sg.begin + (uint32_t)t * (uint32_t)chunk_bytes;
-        limit[t] = t == L - 1 ? 0xFFFFFFFFu : start + (uint32_t)chunk_bytes;
-        ent[t] = ex[t] = jpeg_chunk_fresh(bytes, sg.begin, sg.end, start);
-        sum[t] = JpegChunkSum{0u, 0u, 0u, 0u};
-        if (t < L - 1) jpeg_chunk_speculate(bytes, sg.begin, sg.end, limit[t], q, huff, ent[t], ex[t], sum[t]);
-      }
-      int rounds = 0;
-      for (int r = 0; r < L; ++r) {
-        memcpy(seen, ex, (size_t)L * sizeof(JpegChunkState));   // the barrier
-        int changed = 0;
-        for (int t = 1; t < L; ++t) {
-          if (jpeg_chunk_same(seen[t - 1], ent[t])) continue;
-          ent[t] = seen[t - 1], changed = 1;
-          if (t < L - 1) jpeg_chunk_speculate(bytes, sg.begin, sg.end, limit[t], q, huff, ent[t], ex[t], sum[t]);
-        }
-        ++rounds;
-        if (!changed) break;
-      }
-      uint32_t blk0 = 0, p0 = 0, p1 = 0, p2 = 0;
-      int st_c = 0;
-      int32_t damaged = -1;
-      for (int t = 0; t < L; ++t) {   // (every lane writes, as on the device; the first status in scan order counts)
-        uint32_t at = 0;
-        const int st = jpeg_chunk_write(bytes, sg.begin, sg.end, (uint32_t)total_bytes, limit[t], g, q, huff, kZigzag,
-                                        ent[t], blk0, p0, p1, p2, sg.first_mcu, sg.n_blocks, sg.expect_rst, t == 0,
-                                        coef_c, &at);
-        if (st && !st_c) st_c = st, damaged = (int32_t)at;
-        if (t < L - 1) blk0 += sum[t].blocks, p0 += sum[t].dc0, p1 += sum[t].dc1, p2 += sum[t].dc2;
-      }
+      const int st_s =
+          jpeg_serial_segment(bytes, (uint32_t)total_bytes, g, segs.data(), nseg, huff, kZigzag, k, coef_s);
+      const JpegEmulSegment c = jpeg_emul_chunked_segment(bytes, (uint32_t)total_bytes, g, segs.data(), nseg, huff,
+                                                          kZigzag, chunk_bytes, k, coef_c);
       if (st_s > status_s) status_s = st_s;
-      if (st_c > status_c) status_c = st_c;
-      const int32_t row[5] = {st_s, st_c, rounds, L, damaged};
+      if (c.status > status_c) status_c = c.status;
+      const int32_t row[5] = {st_s, c.status, c.rounds, c.lanes, c.damaged};
       rows.insert(rows.end(), row, row + 5);
     }
     if (g.host_status) status_s = status_c = g.host_status;
@@ -113,7 +71,7 @@ int main(int argc, char** argv) {
     fwrite(rows.data(), 4, rows.size(), out);
     fwrite(coef_s, sizeof(int16_t), 3 * plane, out);
     fwrite(coef_c, sizeof(int16_t), 3 * plane, out);
-    free(sum), free(seen), free(ex), free(ent), free(huff), free(coef_c), free(coef_s), free(bytes);
+    free(huff), free(coef_c), free(coef_s), free(bytes);
   }
   fclose(in);
   return fclose(out) == 0 ? 0 : 2;

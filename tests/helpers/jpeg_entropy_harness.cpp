@@ -1,7 +1,7 @@
 // Host harness of openibl_amd/csrc/jpeg_entropy.h: the text the entropy kernel is made of, compiled without hipcc
 // into a program of its own so that it can run under the host sanitizers (tests/test_jpeg_decode_cpu.py builds it with
 // -fsanitize=address,undefined).  It decodes every case of an input file the way jpeg_entropy_kernel does — the four
-// tables built from the record, one jpeg_decode_segment per row of the segment table — into heap buffers of exactly
+// tables built from the record, one jpeg_serial_segment per row of the segment table — into heap buffers of exactly
 // the sizes the kernel's bounds are stated for, so that any access outside them ends the run.
 //
 //   jpeg_entropy_harness IN OUT
@@ -45,14 +45,9 @@ int main(int argc, char** argv) {
     int16_t* coef = (int16_t*)calloc(3 * plane, sizeof(int16_t));
     JpegHuff* huff = (JpegHuff*)malloc(4 * sizeof(JpegHuff));
     for (int t = 0; t < 4; ++t) jpeg_huff_build(huff + t, rec + JPEG_REC_HUFF + t * JPEG_HUFF_BYTES);
-    const int total = g.mcus_x * g.mcus_y;
-    const int want = jpeg_segments_wanted(total, g.dri);
     int32_t status = 0;
     for (int k = 0; k < g.nseg; ++k) {   // what lane k of the kernel does
-      const int32_t sb = segs[2 * k], se = segs[2 * k + 1];
-      const int st = jpeg_decode_segment(bytes, sb > 0 ? (uint32_t)sb : 0u, se > 0 ? (uint32_t)se : 0u,
-                                         (uint32_t)total_bytes, g, huff, kZigzag, g.dri ? k * g.dri : 0,
-                                         g.dri ? g.dri : total, (g.dri && k + 1 < want) ? (k & 7) : -1, coef);
+      const int st = jpeg_serial_segment(bytes, (uint32_t)total_bytes, g, segs.data(), nseg, huff, kZigzag, k, coef);
       if (st > status) status = st;
     }
     if (g.host_status) status = g.host_status;

@@ -1,10 +1,10 @@
-// Host harness of openibl_amd/csrc/jpeg_mixed.h: the layout function and the entropy stage of csrc/jpeg_mixed.hip on a
-// batch of images of mixed sizes, compiled without hipcc into a program of its own so that it can run under the host
-// sanitizers (tests/test_jpeg_mixed_cpu.py builds it with -fsanitize=address,undefined).  What a kernel of
-// jpeg_mixed.hip does per image is done here per image, with the same shared text: the table row through
+// Host harness of openibl_amd/csrc/jpeg_mixed.h: the layout function and the entropy stage of the jmix_* kernels of
+// csrc/jpeg.hip on a batch of images of mixed sizes, compiled without hipcc into a program of its own so that it can
+// run under the host sanitizers (tests/test_jpeg_mixed_cpu.py builds it with -fsanitize=address,undefined).  What such
+// a kernel does per image is done here per image, with the same shared text: the table row through
 // jpeg_mixed_image against the call's totals, jpeg_geom with the row's H and W, then every segment through
-// jpeg_decode_segment (the serial route) and through the chunk state machine as a workgroup runs it (the chunked
-// route; the loop of tests/helpers/jpeg_chunked_harness.cpp), into ONE coefficient buffer of exactly the layout's size
+// jpeg_serial_segment (the serial route) and through the chunk state machine as a workgroup runs it (the chunked
+// route; the loop of tests/helpers/jpeg_workgroup_emul.h), into ONE coefficient buffer of exactly the layout's size
 // per route, so that an access outside an image's extent that leaves the buffer ends the run, and one that stays
 // inside shows as a difference from the same image decoded alone.
 //
@@ -14,7 +14,7 @@
 //        the geometry table behind the layout function (an inconsistent table)
 //   OUT: int32 geom[N][8], int64 totals[6], then per image int32 {status serial, status chunked, status alone, ok,
 //        ncoef}, int16 alone[ncoef], int16 serial[ncoef], int16 chunked[ncoef] (ncoef = 0 for an image the table check
-//        refuses; `alone`: the image decoded on its own by jpeg_decode_segment into a buffer of its own)
+//        refuses; `alone`: the image decoded on its own by jpeg_serial_segment into a buffer of its own)
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -23,65 +23,11 @@
 
 #include "jpeg_chunked.h"
 #include "jpeg_mixed.h"
+#include "jpeg_workgroup_emul.h"
 
 static const uint8_t kZigzag[64] = {JPEG_ZIGZAG_LIST};
-static const int kMaxLanes = 1024;   // JSCAN_MAX_LANES
 
 static bool get(FILE* f, void* p, size_t n) { return n == 0 || fread(p, 1, n, f) == n; }
-
-// segment k of an image as jpeg_entropy_lane of jpeg_stages.h decodes it
-static int serial_segment(const uint8_t* bytes, uint32_t total_bytes, const JpegGeom& g, const int32_t* segs, int S,
-                          const JpegHuff* huff, int k, int16_t* coef_image) {
-  if (k >= g.nseg || g.seg_first > S - 1 - k) return 0;
-  const int sidx = g.seg_first + k;
-  const int total = g.mcus_x * g.mcus_y;
-  const int want = jpeg_segments_wanted(total, g.dri);
-  const int32_t sb = segs[2 * sidx], se = segs[2 * sidx + 1];
-  return jpeg_decode_segment(bytes, sb > 0 ? (uint32_t)sb : 0u, se > 0 ? (uint32_t)se : 0u, total_bytes, g, huff,
-                             kZigzag, g.dri ? k * g.dri : 0, g.dri ? g.dri : total,
-                             (g.dri && k + 1 < want) ? (k & 7) : -1, coef_image);
-}
-
-// segment k as the workgroup of jpeg_chunked_segment decodes it
-static int chunked_segment(const uint8_t* bytes, uint32_t total_bytes, const JpegGeom& g, const int32_t* segs, int S,
-                           const JpegHuff* huff, int chunk_bytes, int k, int16_t* coef_image) {
-  if (k >= g.nseg || g.seg_first > S - 1 - k) return 0;
-  const int sidx = g.seg_first + k;
-  const JpegChunkGeom q = jpeg_chunk_geom(g);
-  const JpegChunkSeg sg =
-      jpeg_chunk_segment(g, q, k, segs[2 * sidx], segs[2 * sidx + 1], total_bytes, chunk_bytes, kMaxLanes);
-  const int L = sg.lanes;
-  std::vector<JpegChunkState> ent(L), ex(L), seen(L);
-  std::vector<JpegChunkSum> sum(L);
-  std::vector<uint32_t> limit(L);
-  for (int t = 0; t < L; ++t) {
-    const uint32_t start = sg.begin + (uint32_t)t * (uint32_t)chunk_bytes;
-    limit[t] = t == L - 1 ? 0xFFFFFFFFu : start + (uint32_t)chunk_bytes;
-    ent[t] = ex[t] = jpeg_chunk_fresh(bytes, sg.begin, sg.end, start);
-    sum[t] = JpegChunkSum{0u, 0u, 0u, 0u};
-    if (t < L - 1) jpeg_chunk_speculate(bytes, sg.begin, sg.end, limit[t], q, huff, ent[t], ex[t], sum[t]);
-  }
-  for (int r = 0; r < L; ++r) {
-    seen = ex;   // the barrier
-    int changed = 0;
-    for (int t = 1; t < L; ++t) {
-      if (jpeg_chunk_same(seen[t - 1], ent[t])) continue;
-      ent[t] = seen[t - 1], changed = 1;
-      if (t < L - 1) jpeg_chunk_speculate(bytes, sg.begin, sg.end, limit[t], q, huff, ent[t], ex[t], sum[t]);
-    }
-    if (!changed) break;
-  }
-  uint32_t blk0 = 0, p0 = 0, p1 = 0, p2 = 0;
-  int status = 0;
-  for (int t = 0; t < L; ++t) {
-    uint32_t at = 0;
-    const int st = jpeg_chunk_write(bytes, sg.begin, sg.end, total_bytes, limit[t], g, q, huff, kZigzag, ent[t], blk0,
-                                    p0, p1, p2, sg.first_mcu, sg.n_blocks, sg.expect_rst, t == 0, coef_image, &at);
-    if (st && !status) status = st;
-    if (t < L - 1) blk0 += sum[t].blocks, p0 += sum[t].dc0, p1 += sum[t].dc1, p2 += sum[t].dc2;
-  }
-  return status;
-}
 
 int main(int argc, char** argv) {
   if (argc != 3) return fprintf(stderr, "usage: %s IN OUT\n", argv[0]), 2;
@@ -141,12 +87,13 @@ int main(int argc, char** argv) {
       d.alone.assign((size_t)3 * g.Bw * g.Bh * 64, 0);
       d.st_a = 0;
       for (int k = 0; k < g.nseg; ++k) {
-        const int st = serial_segment(bytes, (uint32_t)scan_len, g, segs.data(), S, huff, k, d.alone.data());
+        const int st = jpeg_serial_segment(bytes, (uint32_t)scan_len, g, segs.data(), S, huff, kZigzag, k,
+                                           d.alone.data());
         if (st > d.st_a) d.st_a = st;
       }
       if (g.host_status) d.st_a = g.host_status;
     }
-    // the image as the kernels of jpeg_mixed.hip see it
+    // the image as the jmix_* kernels see it
     const JpegMixImage im = jpeg_mixed_image(geom.data() + (size_t)n * JPEG_MIX_GEOM_INTS, sp);
     d.ok = im.ok, d.at = (size_t)im.coef * 64, d.n = 0;
     d.st_s = d.st_c = JPEG_ST_BAD_GEOM;
@@ -155,8 +102,10 @@ int main(int argc, char** argv) {
     d.n = (size_t)3 * g.Bw * g.Bh * 64;
     d.st_s = d.st_c = 0;
     for (int k = 0; k < g.nseg; ++k) {
-      const int ss = serial_segment(bytes, (uint32_t)scan_len, g, segs.data(), S, huff, k, coef_s + d.at);
-      const int sc = chunked_segment(bytes, (uint32_t)scan_len, g, segs.data(), S, huff, chunk_bytes, k, coef_c + d.at);
+      const int ss =
+          jpeg_serial_segment(bytes, (uint32_t)scan_len, g, segs.data(), S, huff, kZigzag, k, coef_s + d.at);
+      const int sc = jpeg_emul_chunked_segment(bytes, (uint32_t)scan_len, g, segs.data(), S, huff, kZigzag, chunk_bytes,
+                                               k, coef_c + d.at).status;
       if (ss > d.st_s) d.st_s = ss;
       if (sc > d.st_c) d.st_c = sc;
     }

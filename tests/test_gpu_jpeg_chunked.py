@@ -1,4 +1,4 @@
-"""The chunked route of the device JPEG decoder (csrc/jpeg_chunked.hip, `ops.decode_jpeg(scan="chunked")`, the route
+"""The chunked route of the device JPEG decoder (csrc/jpeg.hip, `ops.decode_jpeg(scan="chunked")`, the route
 names of `input_decode`) against Pillow's own outputs in tests/golden/jpeg_decode.npz and tests/golden/jpeg_chunked.npz
 and against the serial route.  Every comparison is exact: the decoder is integer arithmetic."""
 import numpy as np

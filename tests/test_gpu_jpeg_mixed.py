@@ -1,4 +1,4 @@
-"""JPEG batches of mixed stored sizes on the device (csrc/jpeg_mixed.hip, oibl_resize_u8_mixed of csrc/resize.hip,
+"""JPEG batches of mixed stored sizes on the device (csrc/jpeg.hip, oibl_resize_u8_mixed of csrc/resize.hip,
 ops.decode_jpeg_mixed / resize_u8_mixed / decode_resize_jpeg, jpeg.MixedJpegBatch, the `input_decode` of
 extract_features) against the fixture tests/golden/jpeg_mixed.npz — Pillow's own outputs
 (tests/helpers/make_jpeg_mixed_golden.py) — and against the uniform calls on every file alone.  Every comparison is

@@ -1,4 +1,4 @@
-"""The chunked route of the device JPEG decoder (csrc/jpeg_chunked.h, csrc/jpeg_chunked.hip), without a GPU: the
+"""The chunked route of the device JPEG decoder (csrc/jpeg_chunked.h, csrc/jpeg.hip), without a GPU: the
 chunk state machine's shared text as a host program that emulates the workgroup, under the address and
 undefined-behaviour sanitizers, against the serial route's jpeg_decode_segment on the same input; the C ABI's
 validation; the route selection of the Python layer."""
@@ -238,6 +238,34 @@ def test_abi_workspace_query():
                 (1, 32769, 64, 1, 128), (1, 48, 32769, 1, 128), (2, 48, 64, 1, 128), (1, 48, 64, (1 << 28) + 1, 128),
                 (1, 48, 64, 1, 3), (1, 48, 64, 1, 65537), (1, 48, 64, 1, 0)):
         assert q(*bad) == 0, bad
+
+
+def test_python_rounds_view_lies_where_the_c_layout_puts_it():
+    """`ops._jpeg_rounds` is Python's one copy of the workspace layout: the byte offset of its view, plus the rounds
+    and the planes behind it, must be the size the C queries give — for the uniform sizes (a width and a height that
+    are no multiples of 16, an S that is no multiple of 64) and for a mixed size list."""
+    import ctypes
+    import torch
+    from openibl_amd import jpeg, lib, ops
+    h = lib.load()
+    a256 = lambda v: (v + 255) // 256 * 256        # noqa: E731
+
+    def offset(need, coef_bytes, S):
+        ws = torch.empty(need, dtype=torch.uint8)
+        view = ops._jpeg_rounds(ws, coef_bytes, S)
+        assert view.dtype == torch.int32 and view.shape == (S,)
+        return view.data_ptr() - ws.data_ptr()
+
+    for N, H, W, S in ((1, 8, 8, 1), (4, 48, 64, 4), (2, 37, 53, 65), (3, 120, 161, 100), (1, 17, 31, 257)):
+        need = h.oibl_jpeg_decode_chunked_workspace_bytes(N, H, W, S, 64)
+        blocks = N * 3 * jpeg.plane_blocks(H, W)
+        assert need > 0 and jpeg.plane_blocks(H, W) == (-(-H // 16) * 2) * (-(-W // 16) * 2)
+        assert offset(need, blocks * 128, S) + a256(4 * S) + a256(blocks * 64) == need, (N, H, W, S)
+    sizes = [(37, 53), (120, 161), (8, 8), (48, 64)]
+    _, totals = jpeg.mixed_layout(sizes)
+    for S in (4, 70):
+        need = h.oibl_jpeg_decode_mixed_workspace_bytes((ctypes.c_size_t * 6)(*totals), len(sizes), S)
+        assert need > 0 and offset(need, totals[0], S) + a256(4 * S) + a256(totals[1]) == need, S
 
 
 def test_the_new_kernel_does_not_spill():

@@ -1,4 +1,4 @@
-"""JPEG batches of mixed stored sizes (csrc/jpeg_mixed.h, csrc/jpeg_mixed.hip, oibl_resize_u8_mixed), without a GPU:
+"""JPEG batches of mixed stored sizes (csrc/jpeg_mixed.h, csrc/jpeg.hip, oibl_resize_u8_mixed), without a GPU:
 the layout function through the C ABI and its numpy twin, the geometry table's device-side check and the mixed entropy
 stage as a host program under the address and undefined-behaviour sanitizers, the C ABI's validation, MixedJpegBatch
 and collate_mixed, and the refusals of the Python layers."""
