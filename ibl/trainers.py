@@ -14,10 +14,18 @@ What differs from the reference, and why:
   * single rank: no gradient all-reduce is added (the reference leaves that to DistributedDataParallel);
   * `augment` (extension, off by default): with an openibl_amd.augment.ColorJitter set, the loader delivers raw uint8
     tuples (`get_transformer_train(..., as_uint8=True)`) and `_parse_data` jitters and normalises them on the device —
-    the reference's ColorJitter runs inside its host transform.
+    the reference's ColorJitter runs inside its host transform;
+  * training from the files' bytes (extension): a loader over `Preprocessor(..., raw=True)` with
+    `collate_fn=openibl_amd.jpeg.collate_tuples` hands over ONE MixedJpegBatch per batch, and `augment` =
+    Compose(DecodeJpeg(), ColorJitter(..., out='uint8'), Resize(h, w)) decodes, jitters and resizes it on the device in
+    the reference's order, for any mix of stored sizes.  The decoder's per-image status is read right behind the
+    iteration's `loss.item()` (it travels to pinned memory with the chain: no further synchronisation) and a damaged
+    file raises RuntimeError with its name.  `prefetch=True` (off by default) runs that chain for batch i + 1 on a
+    side stream while batch i trains.
 The loop itself — meters, one `loss.item()` synchronisation per iteration, the printed line — is the reference's."""
 from __future__ import annotations
 
+import collections
 import time
 
 import torch
@@ -70,19 +78,106 @@ def _augment_tuples(augment, imgs, gpu):
     return out.view(B, N, 3, out.shape[-2], out.shape[-1])
 
 
+def _is_file_tuples(inputs):
+    """Is a loader batch what `openibl_amd.jpeg.collate_tuples` makes: item 0 a MixedJpegBatch with `tuples` set?"""
+    from openibl_amd.jpeg import MixedJpegBatch
+    return isinstance(inputs, (list, tuple)) and len(inputs) > 0 and isinstance(inputs[0], MixedJpegBatch) and \
+        getattr(inputs[0], "tuples", None) is not None
+
+
+def _file_chain(augment):
+    """ValueError unless `augment` is the chain a batch of file bytes needs."""
+    from openibl_amd.augment import Compose, DecodeJpeg, Resize
+    if isinstance(augment, Compose) and isinstance(augment.stages[0], DecodeJpeg):
+        last = augment.stages[-1]
+        if isinstance(last, Resize) and not last.keep_aspect and last.out == "float":
+            return augment
+    raise ValueError(f"a loader batch of file bytes (openibl_amd.jpeg.collate_tuples) needs `augment` to be an "
+                     f"openibl_amd.augment.Compose that starts with DecodeJpeg and ends with a Resize without "
+                     f"keep_aspect and with out='float' — Compose(DecodeJpeg(), ColorJitter(..., out='uint8'), "
+                     f"Resize(height, width)) — got {augment!r}")
+
+
+def _decode_tuples(augment, inputs, gpu, pending):
+    """A `jpeg.collate_tuples` batch (host, pinned or not) -> [B][N][3][H'][W'] float32 on the device, computed on the
+    current stream: decode, jitter in place at the stored sizes, resize.  Nothing is read back: the decoder's statuses
+    follow the chain into pinned memory and are appended to `pending` with the file names, for `_check_files`."""
+    from openibl_amd.jpeg import tuple_names
+    chain = _file_chain(augment)
+    B, N = inputs[0].tuples
+    out = chain(inputs[0].cuda(gpu, non_blocking=True))
+    status = chain.stages[0].last_status
+    host = torch.empty(status.numel(), dtype=torch.int32).pin_memory()
+    host.copy_(status, non_blocking=True)
+    pending.append((host, tuple_names(inputs)))
+    return out.view(B, N, 3, out.shape[-2], out.shape[-1])
+
+
+def _check_files(pending):
+    """The statuses of the oldest batch `_decode_tuples` left behind, read where the stream that used the batch has
+    been drained (behind `loss.item()`); RuntimeError lists the damaged files."""
+    if not pending:
+        return
+    from openibl_amd.jpeg import STATUS_TEXT
+    host, names = pending.popleft()
+    bad = [f"{names[i] if names is not None else f'item {i}'} ({STATUS_TEXT[min(int(s), len(STATUS_TEXT) - 1)]})"
+           for i, s in enumerate(host.tolist()) if s]
+    if bad:
+        pending.clear()
+        raise RuntimeError(f"training input: {len(bad)} damaged JPEG file(s): " + ", ".join(bad))
+
+
+class _Prefetch(object):
+    """`parse(data_loader.next())` of batch i + 1 on a side stream while batch i trains (the trainers' opt-in
+    `prefetch=True`).  `issue()` enqueues the next batch's input chain — copies, decode, jitter, resize — on the side
+    stream (its own `ops.workspace` scratch: those buffers are per stream) and records an event; `take()` makes the
+    current stream wait for that event and hands the tensors over (`record_stream`: they were allocated on the side
+    stream and are read on this one, as openibl_amd.extract.EagerLanes hands its inputs to a lane).  The host runs
+    the batches in order, so the jitter draws what it draws without prefetch."""
+
+    def __init__(self, parse, data_loader, count, gpu):
+        self.parse, self.loader, self.left = parse, data_loader, count
+        self.device = torch.device("cuda", torch.cuda.current_device() if gpu is None else gpu)
+        self.side = torch.cuda.Stream(device=self.device)
+        self.ready = None
+        self.issue()
+
+    def issue(self):
+        if self.left <= 0:
+            return
+        self.left -= 1
+        with torch.cuda.stream(self.side):
+            out = self.parse(self.loader.next())
+            ev = torch.cuda.Event()
+            ev.record(self.side)
+        self.ready = (out, ev)
+
+    def take(self):
+        out, ev = self.ready
+        self.ready = None
+        main = torch.cuda.current_stream(self.device)
+        main.wait_event(ev)
+        for t in (out if isinstance(out, (tuple, list)) else (out,)):
+            t.record_stream(main)
+        return out
+
+
 class Trainer(object):
     """Training module for NetVLAD (CVPR'16, loss_type='triplet') and SARE (ICCV'19, loss_type='sare_ind' or
     'sare_joint').  `model` is an EmbedNet (possibly inside a `.module` container) on the device."""
 
-    def __init__(self, model, margin=0.3, gpu=None, temp=0.07, augment=None):
+    def __init__(self, model, margin=0.3, gpu=None, temp=0.07, augment=None, prefetch=False):
         super(Trainer, self).__init__()
         self.model = model
         self.gpu = gpu
         self.margin = margin
         self.temp = temp
         # None: the loader delivers normalised float tuples (the reference's flow); an
-        # openibl_amd.augment.ColorJitter: it delivers raw uint8 tuples, jittered and normalised on the device
+        # openibl_amd.augment.ColorJitter: it delivers raw uint8 tuples, jittered and normalised on the device; a
+        # Compose that starts with DecodeJpeg: it delivers the files' bytes (jpeg.collate_tuples)
         self.augment = augment
+        self.prefetch = prefetch                    # True: batch i + 1's input chain runs on a side stream
+        self._files = collections.deque()           # statuses of the file batches not yet checked
 
     def train(self, epoch, sub_id, data_loader, optimizer, train_iters,
               print_freq=1, vlad=True, loss_type='triplet'):
@@ -93,12 +188,17 @@ class Trainer(object):
         end = time.time()
         data_loader.new_epoch()
 
+        self._files.clear()
+        ahead = _Prefetch(self._parse_data, data_loader, train_iters, self.gpu) if self.prefetch else None
         for i in range(train_iters):
-            inputs = self._parse_data(data_loader.next())
+            inputs = ahead.take() if ahead else self._parse_data(data_loader.next())
             data_time.update(time.time() - end)
 
             loss = self._forward(inputs, vlad, loss_type)
+            if ahead:
+                ahead.issue()
             losses.update(loss.item())
+            _check_files(self._files)
 
             optimizer.zero_grad()
             loss.backward()
@@ -119,6 +219,8 @@ class Trainer(object):
 
     def _parse_data(self, inputs):
         # [B][tuple size][C][H][W]
+        if _is_file_tuples(inputs):
+            return _decode_tuples(self.augment, inputs, self.gpu, self._files)
         if self.augment is not None:
             return _augment_tuples(self.augment, _stack_tuples(inputs), self.gpu)
         return _stack_tuples(inputs).cuda(self.gpu)
@@ -149,11 +251,13 @@ class SFRSTrainer(object):
     the number of tuples per batch."""
 
     def __init__(self, model, model_cache, margin=0.3,
-                 neg_num=10, gpu=None, temp=[0.07, ], augment=None):
+                 neg_num=10, gpu=None, temp=[0.07, ], augment=None, prefetch=False):
         super(SFRSTrainer, self).__init__()
         self.model = model
         self.model_cache = model_cache
         self.augment = augment      # as Trainer.augment
+        self.prefetch = prefetch    # as Trainer.prefetch
+        self._files = collections.deque()
 
         self.margin = margin
         self.gpu = gpu
@@ -171,8 +275,10 @@ class SFRSTrainer(object):
         end = time.time()
         data_loader.new_epoch()
 
+        self._files.clear()
+        ahead = _Prefetch(self._parse_data, data_loader, train_iters, self.gpu) if self.prefetch else None
         for i in range(train_iters):
-            inputs_easy, inputs_diff = self._parse_data(data_loader.next())
+            inputs_easy, inputs_diff = ahead.take() if ahead else self._parse_data(data_loader.next())
             data_time.update(time.time() - end)
 
             loss_hard, loss_soft = self._forward(inputs_easy, inputs_diff, loss_type, gen)
@@ -181,9 +287,12 @@ class SFRSTrainer(object):
             optimizer.zero_grad()
             loss.backward()
             optimizer.step()
+            if ahead:
+                ahead.issue()
 
             losses_hard.update(loss_hard.item())
             losses_soft.update(loss_soft.item())
+            _check_files(self._files)
 
             batch_time.update(time.time() - end)
             end = time.time()
@@ -201,15 +310,23 @@ class SFRSTrainer(object):
                               losses_soft.val, losses_soft.avg))
 
     def _parse_data(self, inputs):
+        if _is_file_tuples(inputs):
+            # the files' bytes: decoded, jittered (every image once, as below) and resized on the device
+            imgs = _decode_tuples(self.augment, inputs, self.gpu, self._files)
+        else:
+            imgs = self._parse_tensors(inputs)
+        # easy: anchor, positive, neg_num negatives; diff: anchor and the difficult positives behind them
+        imgs_easy = imgs[:, :self.neg_num + 2]
+        imgs_diff = torch.cat((imgs[:, :1], imgs[:, self.neg_num + 2:]), dim=1)
+        return imgs_easy.cuda(self.gpu), imgs_diff.cuda(self.gpu)
+
+    def _parse_tensors(self, inputs):
         imgs = _stack_tuples(inputs)
         if self.augment is not None:
             # every image is jittered once, the anchor included: the easy and the difficult part share the anchor's
             # jittered image, and the teacher and the student see the same inputs_diff, as in the reference
             imgs = _augment_tuples(self.augment, imgs, self.gpu)
-        # easy: anchor, positive, neg_num negatives; diff: anchor and the difficult positives behind them
-        imgs_easy = imgs[:, :self.neg_num + 2]
-        imgs_diff = torch.cat((imgs[:, :1], imgs[:, self.neg_num + 2:]), dim=1)
-        return imgs_easy.cuda(self.gpu), imgs_diff.cuda(self.gpu)
+        return imgs
 
     def _forward(self, inputs_easy, inputs_diff, loss_type, gen):
         _check_loss_type(loss_type)

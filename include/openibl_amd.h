@@ -904,6 +904,33 @@ int oibl_resize_u8_mixed(const uint8_t* packed, size_t packed_bytes, const int32
                          const int32_t* sizes_host, int N, int H2, int W2, int out_kind, const float* mean3_host,
                          const float* std3_host, void* out, void* ws, size_t ws_bytes, void* stream);
 
+/* oibl_color_jitter_u8_mixed: the training colour jitter (oibl_color_jitter_u8) on the packed buffer, between
+ * oibl_jpeg_decode_mixed and oibl_resize_u8_mixed — the reference's order ColorJitter -> Resize for files of any mix
+ * of stored sizes.
+ *   packed [packed_bytes] uint8 (device), geom_dev [N][8] (device, 4-byte aligned; entries 0, 1, 4, 5 are read) as
+ *   above; sizes_host [N][2] int32 = {H, W} (host: it sizes the grid and the workspace and checks the limits).
+ *   records [N] x 32 bytes as for oibl_color_jitter_u8 (device, 4-byte aligned).  NULL: no jitter — with
+ *   out_packed != packed one launch copies the images' bytes, with out_packed == packed nothing is launched.
+ *   out_packed uint8 (device) with the layout of packed: only the bytes of the N images are written.
+ *   out_packed == packed (in place) is supported; any other overlap is not.
+ * The same kernel text as the uniform call, in two launches with the grid (largest part count of the batch, N); a
+ * workgroup outside its image leaves at once.  An image's chunk and part count come from its OWN H_n W_n, so its
+ * integer partial sums, and its bits, are those of oibl_color_jitter_u8 on that image alone, whatever its batch mates
+ * or its position; no atomics, no floating-point reduction.  Every image starts on a multiple of 64 bytes, so it is
+ * read and written with whole dwords; the group of four pixels that holds an image's end goes by bytes and touches
+ * nothing behind H_n W_n 3 — not the padding, not the next image's slot.
+ * On the device every entry of a row is forced into its range, the extent is checked against packed_bytes and the
+ * part count against the grid; an image whose row fails is skipped by both launches: it reads and writes nothing.
+ * 1 <= N <= 65535, every side in [1, 32768], H_n W_n <= 2^28, 1 <= packed_bytes < 2^40; otherwise OIBL_E_INVALID
+ * before anything is launched, with a message that names the image; a short or misaligned (256 bytes) workspace is
+ * OIBL_E_WORKSPACE.  Stream-ordered, capturable, nothing owned.
+ * Workspace (needed with records only): uint64 partial sums [N][largest part count];
+ * oibl_color_jitter_u8_mixed_workspace_bytes returns 0 for what the call rejects. */
+size_t oibl_color_jitter_u8_mixed_workspace_bytes(const int32_t* sizes_host, int N);
+int oibl_color_jitter_u8_mixed(const uint8_t* packed, size_t packed_bytes, const int32_t* geom_dev,
+                               const int32_t* sizes_host, int N, const void* records, uint8_t* out_packed, void* ws,
+                               size_t ws_bytes, void* stream);
+
 /* ---- recall counting ---------------------------------------------------------------- *
  * Replaces the per-query Python loop of evaluate_all and spatial_nms
  * (ibl/evaluators.py:132-140, 149-160).  For every query, the rank (0-based, inside the

@@ -11,7 +11,13 @@ resize — both with PIL's arithmetic, bit for bit — and the normalisation rid
 Limit, only when the HOST resizes (`get_transformer_train(..., as_uint8=True)` with its default resize=True and a
 bare ColorJitter as `augment`): the reference jitters BEFORE Resize, that flow after it.  The two agree bit for bit
 exactly when the stored images already have the target size (Pitts: 640 x 480); otherwise both are valid augmentations
-of the same distribution that differ in rounding.  With the device resize the order is the reference's."""
+of the same distribution that differ in rounding.  With the device resize the order is the reference's.
+
+From the files' bytes (a loader over `Preprocessor(..., raw=True)` with `collate_fn=jpeg.collate_tuples`): `DecodeJpeg`
+in front decodes the batch on the device, files of any mix of stored sizes included — the jitter then runs in place on
+the decoder's packed buffer (`ops.PackedImages`) and the resize turns that into the dense batch:
+
+    augment = Compose(DecodeJpeg(), ColorJitter(0.7, 0.7, 0.7, 0.5, out='uint8'), Resize(480, 640))"""
 from __future__ import annotations
 
 import numbers
@@ -101,16 +107,24 @@ class ColorJitter(object):
                     codes[i, place] = op
         return torch.cat((codes, factors.view(torch.int32), shifts[:, None]), dim=1).contiguous()
 
-    def __call__(self, u8_batch: torch.Tensor, records: Optional[torch.Tensor] = None) -> torch.Tensor:
+    def __call__(self, u8_batch, records: Optional[torch.Tensor] = None):
         """u8_batch [N][H][W][3] uint8 on the device -> the jittered batch (`out`).  `records`: host or device
         records to use instead of drawing (a replay).  With every op disabled nothing but the plain normalisation
-        (or copy) is launched."""
+        (or copy) is launched.
+        An `ops.PackedImages` (what `DecodeJpeg` makes of a MixedJpegBatch) is jittered IN PLACE, every image at its
+        stored size, and handed on: the stage needs out='uint8' then, the Resize behind it normalises."""
+        packed = isinstance(u8_batch, ops.PackedImages)
+        if packed and self.out != "uint8":
+            raise ValueError("ColorJitter: a packed batch of mixed sizes is jittered in place and needs out='uint8' "
+                             "(the Resize behind it hands float on)")
         if records is None:
             if not self.enabled:
                 self.last_records = None
-                return ops.color_jitter(u8_batch, None, out=self.out)
-            records = self.draw(u8_batch.shape[0])
+                return u8_batch if packed else ops.color_jitter(u8_batch, None, out=self.out)
+            records = self.draw(len(u8_batch) if packed else u8_batch.shape[0])
         self.last_records = records
+        if packed:
+            return ops.jitter_packed(u8_batch, records.to(u8_batch.device))
         return ops.color_jitter(u8_batch, records.to(u8_batch.device), out=self.out)
 
     def __repr__(self):
@@ -152,7 +166,12 @@ class Resize(object):
             return aspect_size(self.height, self.width, int(h), int(w))
         return self.height, self.width
 
-    def __call__(self, u8_batch: torch.Tensor) -> torch.Tensor:
+    def __call__(self, u8_batch) -> torch.Tensor:
+        if isinstance(u8_batch, ops.PackedImages):      # mixed stored sizes: only the resized images form a batch
+            if self.keep_aspect:
+                raise ValueError("Resize: a packed batch of mixed sizes cannot be resized with keep_aspect=True: the "
+                                 "images of one batch would get different sizes")
+            return ops.resize_packed(u8_batch, (self.height, self.width), out=self.out)
         if u8_batch.dim() != 4:
             raise ValueError(f"Resize expects [N][H][W][3], got {tuple(u8_batch.shape)}")
         return ops.resize_u8(u8_batch, self.target(u8_batch.shape[1], u8_batch.shape[2]), out=self.out)
@@ -162,11 +181,47 @@ class Resize(object):
                 f"keep_aspect={self.keep_aspect}, out={self.out!r})")
 
 
+class DecodeJpeg(object):
+    """The first stage of a chain that starts from the files' bytes: a `jpeg.MixedJpegBatch` on the device (files of
+    any mix of stored sizes; `jpeg.collate_tuples`, `jpeg.collate_mixed`) becomes an `ops.PackedImages` — the packed
+    pixel buffer, the sizes, the device's geometry table and the per-image status, which stays on the device
+    (`last_status`; nothing is read back here) — and a `jpeg.JpegBatch` of one size the dense uint8 batch
+    [N][H][W][3].  scan: the route of `ops.decode_jpeg` ("auto", "serial", "chunked")."""
+
+    out = "uint8"
+
+    def __init__(self, scan: str = "auto"):
+        from . import jpeg
+        if scan not in jpeg.SCAN_ROUTES:
+            raise ValueError(f"DecodeJpeg: scan must be one of {jpeg.SCAN_ROUTES}, not {scan!r}")
+        self.scan = scan
+        self.last_status = None     # int32 [N] on the device: the statuses of the last call
+
+    def __call__(self, batch):
+        from . import jpeg
+        if isinstance(batch, jpeg.MixedJpegBatch):
+            images = ops.decode_jpeg_packed(batch, scan=self.scan)
+            self.last_status = images.status
+            return images
+        if isinstance(batch, jpeg.JpegBatch):
+            pixels, self.last_status = ops.decode_jpeg(batch, check=False, scan=self.scan)
+            return pixels
+        raise ValueError(f"DecodeJpeg decodes a MixedJpegBatch or a JpegBatch (a loader over Preprocessor(..., "
+                         f"raw=True) with collate_fn=openibl_amd.jpeg.collate_tuples / collate_mixed / collate), got "
+                         f"{type(batch).__name__}")
+
+    def __repr__(self):
+        return f"{self.__class__.__name__}(scan={self.scan!r})"
+
+
 class Compose(object):
     """Chains stages on a device batch: Compose(a, b)(x) = b(a(x)).  Every stage but the last must hand uint8 on
     (out='uint8').  The reference's training transform is
     Compose(ColorJitter(0.7, 0.7, 0.7, 0.5, out='uint8'), Resize(480, 640)).
-    Keyword arguments of a call go to the FIRST stage (the `records=` of a ColorJitter replay)."""
+    Keyword arguments of a call go to the FIRST stage (the `records=` of a ColorJitter replay); `records=` reaches
+    the ColorJitter stage wherever it stands — behind a DecodeJpeg for instance:
+    Compose(DecodeJpeg(), ColorJitter(0.7, 0.7, 0.7, 0.5, out='uint8'), Resize(480, 640)) is the whole chain from the
+    files' bytes."""
 
     def __init__(self, *stages):
         if not stages:
@@ -179,10 +234,12 @@ class Compose(object):
                                  f"out='uint8'")
         self.stages = tuple(stages)
 
-    def __call__(self, batch: torch.Tensor, **first_stage_args) -> torch.Tensor:
-        batch = self.stages[0](batch, **first_stage_args)
-        for stage in self.stages[1:]:
-            batch = stage(batch)
+    def __call__(self, batch, **first_stage_args) -> torch.Tensor:
+        at = 0
+        if "records" in first_stage_args and not isinstance(self.stages[0], ColorJitter):
+            at = next((k for k, s in enumerate(self.stages) if isinstance(s, ColorJitter)), 0)
+        for k, stage in enumerate(self.stages):
+            batch = stage(batch, **first_stage_args) if k == at else stage(batch)
         return batch
 
     def __repr__(self):

@@ -533,3 +533,35 @@ def collate_mixed(items, target=None):
     collated as usual.  target = (h, w), the size of the resize behind the decoder, makes an image beyond the resize's
     shrink limit a ValueError in the worker: `collate_fn=functools.partial(jpeg.collate_mixed, target=(480, 640))`."""
     return _collate(items, lambda files: MixedJpegBatch.from_files(files, target=target))
+
+
+def collate_tuples(items, target=None):
+    """DataLoader `collate_fn` for a TUPLE sampler over `Preprocessor(..., raw=True)` (the training loaders): `items`
+    are B tuples, each a list of N items (bytes, fname, pid, x, y).  Item 0 of the result is ONE MixedJpegBatch of the
+    B * N files in tuple-major order (file n of tuple b at b * N + n) with the attribute `tuples = (B, N)` — always a
+    mixed batch, whether or not the stored sizes agree — for a trainer whose `augment` starts with
+    `augment.DecodeJpeg`.  The other fields follow as `default_collate` collates them for such a loader: one entry per
+    tuple position n, the list [fnames (B), pids [B], x [B], y [B]].  target = (h, w) as for `collate_mixed`: an image
+    beyond the resize's shrink limit is a ValueError in the worker.  Tuples of unequal length are a ValueError."""
+    from torch.utils.data import default_collate
+    items = [list(t) for t in items]
+    if not items or not items[0]:
+        raise ValueError("collate_tuples: an empty batch")
+    B, N = len(items), len(items[0])
+    for b, t in enumerate(items):
+        if len(t) != N:
+            raise ValueError(f"collate_tuples: tuple {b} has {len(t)} images, tuple 0 has {N}: the tuples of a batch "
+                             f"must have one length")
+    batch = MixedJpegBatch.from_files([it[0] for t in items for it in t], target=target)
+    batch.tuples = (B, N)
+    rest = default_collate([[tuple(it[1:]) for it in t] for t in items]) if len(items[0][0]) > 1 else []
+    return [batch] + list(rest)
+
+
+def tuple_names(batch):
+    """The file names of a `collate_tuples` batch in the order of its MixedJpegBatch (b * N + n), or None."""
+    B, N = batch[0].tuples
+    rest = batch[1:]
+    if len(rest) != N or not all(isinstance(r, (list, tuple)) and r and len(r[0]) == B for r in rest):
+        return None
+    return [str(rest[n][0][b]) for b in range(B) for n in range(N)]

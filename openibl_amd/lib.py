@@ -206,6 +206,9 @@ SIGNATURES = {
     "oibl_resize_u8_mixed_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int]),
     "oibl_resize_u8_mixed": (c_int, [c_void_p, c_size_t, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p,
                                      c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "oibl_color_jitter_u8_mixed_workspace_bytes": (c_size_t, [c_void_p, c_int]),
+    "oibl_color_jitter_u8_mixed": (c_int, [c_void_p, c_size_t, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                           c_size_t, c_void_p]),
     "oibl_cluster_means": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "oibl_local_descriptors": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     "oibl_assign_gap_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),

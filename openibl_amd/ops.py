@@ -2359,3 +2359,164 @@ def decode_resize_jpeg(batch, size, out: str = "uint8", check: bool = True, scan
         return res, status
     _raise_damaged("decode_resize_jpeg", status)
     return res
+
+
+# ---------------------------------------------------------------------------------------------
+def _jitter_params(what, params, N):
+    if params is None:
+        return
+    if not torch.is_tensor(params) or params.dtype != torch.int32:
+        raise ValueError(f"{what}: params must be int32 records, got {getattr(params, 'dtype', type(params).__name__)}")
+    if tuple(params.shape) != (N, JITTER_RECORD_WORDS):
+        raise ValueError(f"{what}: params must be [{N}][{JITTER_RECORD_WORDS}], got {tuple(params.shape)}")
+    if not params.is_contiguous():
+        raise ValueError("openibl_amd: tensors must be contiguous")
+
+
+def _jitter_sizes(what, sizes):
+    """The limits of oibl_color_jitter_u8_mixed on the host's sizes (the layout's own come from `jpeg.mixed_layout`)."""
+    if sizes.shape[0] > 65535:
+        raise ValueError(f"{what}: N <= 65535, got {sizes.shape[0]} images")
+    for i, (h, w) in enumerate(sizes.tolist()):
+        if h >= 1 and w >= 1 and h * w > JITTER_MAX_PIXELS:
+            raise ValueError(f"{what}: image {i} is {h} x {w}: more than 2^28 pixels")
+
+
+def color_jitter_mixed(packed: torch.Tensor, sizes, params: Optional[torch.Tensor], out=None) -> torch.Tensor:
+    """Training colour jitter of a PACKED batch of mixed sizes on the device (oibl_color_jitter_u8_mixed), PIL's bits:
+    packed is the 1-D uint8 tensor that holds image i as [H_i][W_i][3] at the offset `jpeg.mixed_layout(sizes)` gives
+    it (what `decode_jpeg_mixed` writes and `resize_u8_mixed` reads), sizes int [N][2] = {H_i, W_i} on the host,
+    `params` int32 [N][8] on the device as for `color_jitter`, or None for no jitter.  out=None allocates a new packed
+    buffer, out=packed works in place; the jittered packed buffer is returned.  Every image equals
+    `color_jitter(image[None], params[i:i + 1], out='uint8')` of that image alone; the padding between the images is
+    never written."""
+    from . import jpeg as _jpeg
+    what = "color_jitter_mixed"
+    if not torch.is_tensor(packed) or packed.dtype != torch.uint8 or packed.dim() != 1:
+        raise ValueError(f"{what} expects a 1-D uint8 packed buffer, got "
+                         f"{getattr(packed, 'dtype', type(packed).__name__)} {tuple(getattr(packed, 'shape', ()))}")
+    sizes = _mixed_sizes(sizes, what)
+    N = sizes.shape[0]
+    _jitter_sizes(what, sizes)
+    geom, totals = _jpeg.mixed_layout(sizes)
+    if packed.numel() < totals[2]:
+        raise ValueError(f"{what}: the packed buffer has {packed.numel()} bytes, the images need {totals[2]}")
+    _jitter_params(what, params, N)
+    if out is not None:
+        if not torch.is_tensor(out) or out.dtype != torch.uint8 or out.dim() != 1 or out.numel() != packed.numel():
+            raise ValueError(f"{what}: out must be a 1-D uint8 buffer of the packed buffer's {packed.numel()} bytes "
+                             f"(or the packed buffer itself)")
+        if out.device != packed.device:
+            raise ValueError(f"{what}: out must be on the packed buffer's device")
+    if not packed.is_contiguous() or (out is not None and not out.is_contiguous()):
+        raise ValueError("openibl_amd: tensors must be contiguous")
+    dev = _need_cuda(packed, params)
+    if out is None:
+        out = torch.empty_like(packed)
+    return _color_jitter_mixed(packed, torch.from_numpy(geom).to(dev, non_blocking=True), sizes, params, out, dev)
+
+
+def _color_jitter_mixed(packed, geom_dev, sizes, params, out, dev):
+    lib = _lib.load()
+    N = sizes.shape[0]
+    sp = sizes.ctypes.data_as(C.c_void_p)
+    ws = None
+    if params is not None:
+        ws = workspace(lib.oibl_color_jitter_u8_mixed_workspace_bytes(sp, N), dev, slot="color_jitter")
+    _lib.check(lib.oibl_color_jitter_u8_mixed(_ptr(packed), packed.numel(), _ptr(geom_dev), sp, N, _ptr(params),
+                                              _ptr(out), _ptr(ws), 0 if ws is None else ws.numel(), _stream(dev)),
+               "color_jitter_u8_mixed")
+    return out
+
+
+class PackedImages:
+    """A MixedJpegBatch decoded on the device: `packed`, the 1-D uint8 buffer that holds image i as [H_i][W_i][3] at
+    its offset of `geom` (int32 [N][8] on the device, the batch's geometry table), `sizes` (int32 numpy [N][2] on the
+    host) and `status` (int32 [N] on the device, the decoder's per-image status: `jpeg.STATUS_TEXT`).  What
+    `color_jitter_mixed` works on in place and `resize_u8_mixed` turns into the dense batch."""
+
+    def __init__(self, packed, sizes, geom, status):
+        self.packed, self.sizes, self.geom, self.status = packed, sizes, geom, status
+
+    def __len__(self):
+        return int(self.sizes.shape[0])
+
+    @property
+    def device(self):
+        return self.packed.device
+
+
+def decode_jpeg_packed(batch, scan: str = "auto", chunk_bytes=None) -> PackedImages:
+    """Decode a `jpeg.MixedJpegBatch` on the device into its packed buffer (`PackedImages`), without reading the
+    statuses back; the files of the host route are copied into their slots."""
+    packed, status = _decode_jpeg_mixed_packed(batch, scan, chunk_bytes)
+    return PackedImages(packed, _mixed_sizes(batch.sizes, "decode_jpeg_mixed"), batch.geom, status)
+
+
+def jitter_packed(images: PackedImages, params: Optional[torch.Tensor]) -> PackedImages:
+    """`color_jitter_mixed` in place on a `PackedImages`; params int32 [N][8] on the device, or None."""
+    what = "color_jitter_mixed"
+    _jitter_sizes(what, images.sizes)
+    _jitter_params(what, params, len(images))
+    dev = _need_cuda(images.packed, images.geom, params)
+    if params is not None:
+        _color_jitter_mixed(images.packed, images.geom, images.sizes, params, images.packed, dev)
+    return images
+
+
+def resize_packed(images: PackedImages, size, out: str = "uint8", mean=REF_MEAN, std=REF_STD) -> torch.Tensor:
+    """`resize_u8_mixed` of a `PackedImages`: the dense batch [N][height][width][3] uint8 or, out='float',
+    [N][3][height][width] float32 normalised."""
+    from . import jpeg as _jpeg
+    what = "resize_u8_mixed"
+    if out not in JITTER_OUT:
+        raise ValueError(f"{what}: out must be 'float' or 'uint8', not {out!r}")
+    if not isinstance(size, (tuple, list)) or len(size) != 2:
+        raise ValueError(f"{what}: size must be (height, width), got {size!r}")
+    H2, W2 = int(size[0]), int(size[1])
+    if H2 > RESIZE_MAX_DIM or W2 > RESIZE_MAX_DIM:
+        raise ValueError(f"{what}: every size <= {RESIZE_MAX_DIM}, got -> {H2} x {W2}")
+    _jpeg.check_shrink(images.sizes, (H2, W2), what)
+    dev = _need_cuda(images.packed, images.geom)
+    return _resize_u8_mixed(images.packed, images.geom, images.sizes, H2, W2, out, mean, std, dev)
+
+
+def decode_jitter_resize_jpeg(batch, params: Optional[torch.Tensor], size, out: str = "float", check: bool = True,
+                              scan: str = "auto", chunk_bytes=None, mean=REF_MEAN, std=REF_STD):
+    """From files to the jittered training batch on the device, in the reference's order ColorJitter -> Resize ->
+    ToTensor -> Normalize: decode a `jpeg.MixedJpegBatch` (any mix of stored sizes) into the packed buffer, jitter
+    every image in place at its stored size (`params` int32 [N][8] on the device as for `color_jitter`, or None) and
+    resize it to size = (height, width) — [N][3][height][width] float32 normalised, or with out='uint8'
+    [N][height][width][3].  Every image has the bytes of PIL's decode, torchvision's ColorJitter with the record's
+    order and factors, and `resize((width, height), Image.BILINEAR)`; the files of the host route (progressive, PNG,
+    CMYK, narrower than 8 pixels) are jittered with the rest.  A plain `jpeg.JpegBatch` takes the uniform calls,
+    `resize_u8(color_jitter(decode_jpeg(batch), params, out='uint8'), size, out=out)`.  check=False returns
+    (batch, status) without a sync."""
+    from . import jpeg as _jpeg
+    what = "decode_jitter_resize_jpeg"
+    if not isinstance(size, (tuple, list)) or len(size) != 2:
+        raise ValueError(f"{what}: size must be (height, width), got {size!r}")
+    if out not in JITTER_OUT:
+        raise ValueError(f"{what}: out must be 'float' or 'uint8', not {out!r}")
+    if isinstance(batch, _jpeg.JpegBatch):
+        _jitter_params(what, params, batch.n)
+        pixels, status = decode_jpeg(batch, check=False, scan=scan, chunk_bytes=chunk_bytes)
+        res = resize_u8(color_jitter(pixels, params, out="uint8"), size, out=out, mean=mean, std=std)
+    else:
+        if not isinstance(batch, _jpeg.MixedJpegBatch):
+            raise ValueError(f"{what} expects a MixedJpegBatch or a JpegBatch (openibl_amd.jpeg.collate_tuples / "
+                             f"collate_mixed / collate), got {type(batch).__name__}")
+        H2, W2 = int(size[0]), int(size[1])
+        sizes = _mixed_sizes(batch.sizes, what)
+        if H2 > RESIZE_MAX_DIM or W2 > RESIZE_MAX_DIM:
+            raise ValueError(f"{what}: every size <= {RESIZE_MAX_DIM}, got -> {H2} x {W2}")
+        _jpeg.check_shrink(sizes, (H2, W2), what)
+        _jitter_sizes(what, sizes)
+        _jitter_params(what, params, batch.n)
+        images = jitter_packed(decode_jpeg_packed(batch, scan, chunk_bytes), params)
+        res = _resize_u8_mixed(images.packed, images.geom, sizes, H2, W2, out, mean, std, images.device)
+        status = images.status
+    if not check:
+        return res, status
+    _raise_damaged(what, status)
+    return res
